@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — images/s of the MAF-YOLO-n hot path on MI355X (BASELINE.json metric, configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 with no launcher around it re-executes itself as the line below)
+    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 with no launcher around it runs itself as the line below, in a child process)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -29,10 +29,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# The serving loop keeps three batches in flight on three streams plus one for the NMS.  ROCm multiplexes a process's streams onto
-# GPU_MAX_HW_QUEUES hardware queues (default 4) and streams that share a queue run one after the other: give them room.  (Must be set
-# before the HIP runtime starts, i.e. before torch is imported; an explicit setting in the environment wins.)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 # multi-process GPU work on this pool: the host driver supports dmabuf IPC only (without this RCCL fails with hipIpcGetMemHandle: invalid argument); already exported on the
 # boxes, set here too so that a bare `python bench.py --gpus N` cannot miss it
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -103,7 +99,7 @@ def latency_leg(torch, M, dev, scale, n, warmup, lanes=-1):
 
 
 def latency_mode(args, torch, M, dev):
-    print(json.dumps(latency_leg(torch, M, dev, args.scale, max(args.steps, 200), args.warmup, args.lanes)), flush=True)
+    print(json.dumps(latency_leg(torch, M, dev, args.scale, args.steps, args.warmup, args.lanes)), flush=True)
 
 
 def infer_leg(torch, M, dev, scale, batch, steps, warmup, cs=None):
@@ -449,10 +445,12 @@ def train_mode(args, torch, M, dev, rank, world, dist):
 
 
 def self_launch(n):
-    """`python bench.py --gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset): replace this process by the launch the docstring names —
+    """`python bench.py --gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset): run the launch the docstring names —
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free port> bench.py <same arguments>` — one rank
-    per GPU (tools/train.py:109-114 reads the same LOCAL_RANK / RANK / WORLD_SIZE).  Runs before torch is imported; does not return."""
+    per GPU (tools/train.py:109-114 reads the same LOCAL_RANK / RANK / WORLD_SIZE) as a child process, and exit with its status.  Runs before torch is
+    imported; does not return."""
     import socket
+    import subprocess
     so = socket.socket()
     so.bind(("127.0.0.1", 0))
     port = so.getsockname()[1]
@@ -461,7 +459,24 @@ def self_launch(n):
            os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execv(sys.executable, cmd)
+    rc = subprocess.call(cmd)
+    sys.exit(rc if rc >= 0 else 128 - rc)                      # killed by signal s: 128 + s, as a shell reports it
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, dets):
+    """--dump-outputs: what the last timed step handed its caller — the detections of every image of its batch, float32 rows (x1, y1, x2, y2,
+    score, class) — as path/detections_<image>.npy, for comparing two builds output for output."""
+    import numpy as np
+    arrs = [d.detach().float().cpu().numpy() for d in dets]
+    total = sum(a.nbytes for a in arrs)
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes of detections exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for i, a in enumerate(arrs):
+        np.save(os.path.join(path, "detections_%03d.npy" % i), a)
 
 
 def rendezvous_only(args, rank, world):
@@ -524,18 +539,25 @@ def main():
     ap.add_argument("--rendezvous-only", action="store_true", help="N > 1: launch, process group, barrier / MAX-over-ranks protocol and the JSON line only — no device work (the CPU test of the launch path)")
     ap.add_argument("--latency", action="store_true",
                     help="BASELINE configs[4] instead: bs=1 forward replayed from a hipGraph + fused NMS, p50/p99 latency (use with --scale m)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the detections of the last timed step, one float32 DIR/detections_<image>.npy per image of its batch")
     args = ap.parse_args()
-
-    import numpy as np
-    import torch
-    import maf_yolo_amd as M
-    from maf_yolo_amd import lib
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.train or args.latency or args.rendezvous_only):
+        ap.error("--dump-outputs writes the outputs of the default workload (forward + NMS); --train, --latency and --rendezvous-only have none")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)                 # `python bench.py --gpus N` as typed for N = 1: becomes the N-rank launch (does not return)
+
+    import numpy as np
+    import torch
+    import maf_yolo_amd as M
+    from maf_yolo_amd import lib
+
     if args.gpus > 1 and world != args.gpus:
         raise SystemExit("bench.py --gpus %d was started with WORLD_SIZE=%d: launch it with --nproc-per-node %d, or with no launcher at all" % (args.gpus, world, args.gpus))
     if args.rendezvous_only:
@@ -667,6 +689,8 @@ def main():
         elapsed = t.item()
     ms_step = 1e3 * elapsed / args.steps
     value = world * B * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dets)
     from maf_yolo_amd.streams import overlap_ratio
     probe1 = overlap_ratio(cs)
     arenas = [model.plan_for(x, slot=k).arena.data_ptr() for k in range(S)]

@@ -1,6 +1,6 @@
 """HIP streams that really run side by side.
 
-ROCm multiplexes the streams of a process onto a few hardware queues (4 by default, GPU_MAX_HW_QUEUES); two streams that land on the
+ROCm multiplexes the streams of a process onto a few hardware queues (four by default; the environment may set fewer); two streams that land on the
 same queue execute their kernels strictly one after the other.  A serving loop that keeps two batches in flight on two streams
 (Model.forward(x, slot=k), bench.py) then silently loses the overlap — measured: 1.58 ms per forward on two queues, 2.0 ms when the
 streams alias.  `concurrent_streams` creates streams until it has `n` that demonstrably overlap (timed with spin kernels)."""

@@ -176,9 +176,35 @@ so = socket.socket(); so.bind(("127.0.0.1", 0)); port = so.getsockname()[1]; so.
 dist.init_process_group("nccl", init_method="tcp://127.0.0.1:%%d" %% port, rank=0, world_size=1, device_id=dev)
 m = M.Model("n"); m.load_state_dict(synth.synth_state_dict(m, "n", 0)); m = m.to(dev).train()
 x = synth.synth_images(32, 640, seed=3).to(dev)
-# two streams on different hardware queues (streams that share a queue run one after the other, and the legacy default stream synchronises
-# with every other stream): the step runs on cs[0], the weight gradients and the collectives on cs[1]
-cs = M.concurrent_streams(dev, 2)
+# the step runs on a main stream, the weight gradients and the collectives on a side stream; neither may be the legacy default stream (it
+# synchronises with every other stream).  A collective runs on RCCL's own stream, which first waits for the side stream.  Streams that share a
+# hardware queue run one after the other, and a process may get fewer queues than the three streams: RCCL's stream can then share the main
+# stream's queue, and its wait holds the main stream too.  So issue one collective (RCCL's stream exists from then on) and take a pair on which
+# a main-stream kernel finishes while a collective waits behind a spin on the side stream.
+t0 = torch.cuda.Event(enable_timing=True); t1 = torch.cuda.Event(enable_timing=True)
+t0.record(); torch.cuda._sleep(20_000_000); t1.record(); torch.cuda.synchronize()
+per_cycle = t0.elapsed_time(t1) / 20_000_000
+probe = torch.ones(256, device=dev)
+dist.all_reduce(probe); torch.cuda.synchronize()
+def main_runs_past_a_waiting_collective(main, side):
+    ev = {k: torch.cuda.Event(enable_timing=True) for k in ("start", "spin_end", "main_end")}
+    torch.cuda.synchronize()
+    ev["start"].record(main)
+    side.wait_event(ev["start"])
+    with torch.cuda.stream(side):
+        torch.cuda._sleep(int(40.0 / per_cycle))
+        ev["spin_end"].record()
+        dist.all_reduce(probe, async_op=True)
+    with torch.cuda.stream(main):
+        torch.cuda._sleep(1000)
+        ev["main_end"].record()
+    torch.cuda.synchronize()
+    return ev["start"].elapsed_time(ev["main_end"]) < 0.5 * ev["start"].elapsed_time(ev["spin_end"])
+pool = [torch.cuda.Stream(dev) for _ in range(6)]
+pair = next(((a, b) for a in pool for b in pool if a is not b and main_runs_past_a_waiting_collective(a, b)), None)
+if pair is None:
+    raise SystemExit("no (main, side) stream pair on which the main stream runs while a collective waits for the side stream")
+cs = list(pair)
 train_ops._side_streams[dev.index] = cs[1]; train_ops._side_events[dev.index] = torch.cuda.Event()
 torch.cuda.synchronize()
 torch.cuda.set_stream(cs[0])
@@ -235,7 +261,7 @@ print("RESULT " + json.dumps(res))
 def test_rccl_branch_on_one_gpu_all_reduce_from_the_side_stream():
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", GPU_MAX_HW_QUEUES="8")
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-c", _RCCL1 % {"root": root}], capture_output=True, text=True, timeout=540, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     res = json.loads([l for l in r.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])

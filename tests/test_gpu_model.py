@@ -738,10 +738,14 @@ def test_two_batches_in_flight_on_two_streams_give_the_single_stream_result(mode
 
 def test_concurrent_streams_overlap():
     """streams.concurrent_streams: the streams it returns run spin kernels side by side (streams that alias onto one hardware queue —
-    which plain torch.cuda.Stream() pairs sometimes do — would take n times as long)."""
+    which plain torch.cuda.Stream() pairs sometimes do — would take n times as long).  Three streams, or as many as the hardware queues the
+    environment grants a process, if that is fewer: beyond that even distinct queues cannot be had."""
+    import os
     import time
-    ss = M.concurrent_streams(DEV, 3)
-    assert len({s.cuda_stream for s in ss}) == 3
+    cap = os.environ.get("GPU_MAX_HW_QUEUES")
+    n = 3 if cap is None else max(2, min(3, int(cap)))
+    ss = M.concurrent_streams(DEV, n)
+    assert len({s.cuda_stream for s in ss}) == n
     def spin(streams):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -752,8 +756,8 @@ def test_concurrent_streams_overlap():
         return time.perf_counter() - t0
     spin(ss[:1])
     one = min(spin(ss[:1]) for _ in range(3))
-    three = min(spin(ss) for _ in range(3))
-    assert three < 2.0 * one, (one, three)
+    together = min(spin(ss) for _ in range(3))
+    assert together < (n + 1) / 2 * one, (n, one, together)           # two streams on one queue: n = 3 -> 2x, n = 2 -> 2x
 
 
 def test_async_nms_of_fp16_and_strided_predictions_is_ordered_after_their_producer(models):
@@ -988,17 +992,18 @@ def test_config4_tuned_bs1_plan_matches_oracle():
     assert np.array_equal(dets[0].cpu().numpy(), odets[0]) and np.array_equal(idx[0].cpu().numpy(), oidx[0])
 
 
-def test_bench_line_contract():
+def test_bench_line_contract(tmp_path):
     """`python bench.py` prints ONE JSON line with the fields the driver reads (metric, value, unit, n_gpus, steps, warmup, ms_per_step,
     higher_is_better, scaling, vs_baseline, dtype, data, config.workload) plus the roofline object of the dominant kernel; a short run at
-    batch 8 without tuning or the CPU leg."""
+    batch 8 without tuning or the CPU leg.  `--dump-outputs` leaves the last timed step's detections, one float32 array per image."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--batch", "8", "--steps", "6", "--warmup", "3", "--no-cpu-baseline", "--no-autotune"],
-                         cwd=root, capture_output=True, text=True, timeout=900)
+    dump = str(tmp_path / "outputs")
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--batch", "8", "--steps", "6", "--warmup", "3", "--no-cpu-baseline", "--no-autotune",
+                          "--dump-outputs", dump], cwd=root, capture_output=True, text=True, timeout=900)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]
     d = json.loads(lines[0])
@@ -1017,3 +1022,9 @@ def test_bench_line_contract():
     n = d["nms"]
     assert n["synthetic_head"]["ms_per_batch"] > 0 and n["synthetic_head"]["matrix_form_ms_per_batch"] > 0 and n["classes_spread_80"]["ms_per_batch"] > 0
     assert n["classes_spread_80"]["images_on_per_class_path"] == 8 and n["synthetic_head"]["candidates_per_image"] == n["classes_spread_80"]["candidates_per_image"]
+    assert sorted(os.listdir(dump)) == ["detections_%03d.npy" % i for i in range(8)]
+    rows = [np.load(os.path.join(dump, "detections_%03d.npy" % i)) for i in range(8)]
+    assert all(a.dtype == np.float32 and a.ndim == 2 and a.shape[1] == 6 and a.shape[0] <= 300 for a in rows)
+    a = np.concatenate(rows)
+    assert a.shape[0] > 0 and np.isfinite(a).all() and (a[:, 2] >= a[:, 0]).all() and (a[:, 3] >= a[:, 1]).all()
+    assert (a[:, 4] > 0.0299).all() and (a[:, 5] == np.round(a[:, 5])).all() and (0 <= a[:, 5]).all() and (a[:, 5] < 80).all()

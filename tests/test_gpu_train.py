@@ -904,7 +904,7 @@ def test_bench_train_two_ranks_on_one_device():
 
 @pytest.mark.gpu
 def test_bench_train_self_launch_two_ranks_on_one_device():
-    """`python bench.py --gpus 2 --train ...` with NO launcher (the command line the driver types for N = 1): bench.self_launch re-executes it under
+    """`python bench.py --gpus 2 --train ...` with NO launcher (the command line the driver types for N = 1): bench.self_launch runs it under
     torch.distributed.run; two ranks share cuda:0 over gloo (MAF_BENCH_ONE_DEVICE), the package's GradExchange issues one all-reduce per bucket, and the line
     carries ranks_seen = 2, the bucket sizes and the exposed all-reduce time."""
     import json

@@ -641,7 +641,7 @@ def test_cat_buffer_join_and_fork_are_cat_and_split_for_autograd():
 
 
 def test_bench_launches_itself_for_more_than_one_gpu():
-    """`python bench.py --gpus 2` exactly as the driver types it for N = 1 — no launcher, WORLD_SIZE unset — re-executes itself under torch.distributed.run
+    """`python bench.py --gpus 2` exactly as the driver types it for N = 1 — no launcher, WORLD_SIZE unset — runs itself under torch.distributed.run in a child process
     (bench.self_launch), forms a two-rank group and runs the timing protocol (barrier, MAX over ranks, one JSON line from rank 0).  `--rendezvous-only` keeps the
     device out of it (this container has none); the same launch with kernels is tests/test_gpu_train.py::test_bench_train_self_launch_two_ranks_on_one_device."""
     import json
