@@ -593,6 +593,42 @@ int maf_tape_toggle(const maf_tape_toggle_t* t, int32_t n);
 int maf_coco_rows(const float* rows, const int32_t* count, int32_t B, int32_t max_det, const float* img_params,
                   const int32_t* ids, int32_t n_ids, float* out, int32_t* out_total, maf_stream_t stream);
 
+/*
+ * Letterbox on the device — replaces letterbox() (yolov6/data/data_augment.py:53-82: cv2.resize INTER_LINEAR to new_unpad,
+ * copyMakeBorder with a constant colour) plus the HWC -> CHW / BGR -> RGB of Inferer.precess_image (yolov6/core/inferer.py:169-179), or
+ * TrainValDataset.load_image's resize plus the rect letterbox of __getitem__ (yolov6/data/datasets.py:277-300, :196-213), for a whole batch
+ * in one launch.  The geometry (new_h, new_w, top, left) is computed by the caller (maf-yolo_amd/letterbox.py); the pixel rule is OpenCV's
+ * uint8 INTER_LINEAR as restated in tests/letterbox_ref.py, an exact 2x shrink on both axes is its area-fast average, equal sizes a copy.
+ *   imgs [B]      HOST table, one entry per frame: frame = uint8 HWC (3 channels, channel stride 1, pixel stride 3, row pitch in bytes)
+ *   imgs_dev      device copy of the same table; needed only for B > MAF_LETTERBOX_KARG_MAX (smaller tables travel as kernel arguments)
+ *   H, W          the common output size, positive multiples of 32; top + new_h <= H, left + new_w <= W for every frame
+ *   color [3]     HOST: the border colour, in the frame's channel order (the reference's (114, 114, 114))
+ *   bgr           1: frames are BGR (cv2.imread) and are swapped to RGB as precess_image's [::-1] does; 0: frames are RGB
+ *   out           DEVICE, 4-byte aligned, uint8 [B, 3, H, W] (RGB planes): every byte written exactly once, border included (32-bit stores)
+ *   frames        DEVICE memory; every read stays inside [row * pitch, row * pitch + 3 w) of a row < h
+ * Validates everything above before touching the device.  maf_letterbox_lds_bytes: the launch's LDS size (at most 64 KiB).
+ */
+#define MAF_LETTERBOX_KARG_MAX 64
+typedef struct {
+    const uint8_t* ptr; int64_t pitch;
+    int32_t h, w;                        /* source frame */
+    int32_t new_h, new_w, top, left;     /* unpadded (resized) size and its offset in the output */
+} maf_letterbox_image_t;
+int64_t maf_letterbox_lds_bytes(const maf_letterbox_image_t* imgs, int32_t B, int32_t W);
+int maf_letterbox(const maf_letterbox_image_t* imgs, const maf_letterbox_image_t* imgs_dev, int32_t B, int32_t H, int32_t W,
+                  const uint8_t* color, int32_t bgr, uint8_t* out, maf_stream_t stream);
+
+/*
+ * Inferer.rescale (yolov6/core/inferer.py:181-195) and the .round() of :98, in place on the NMS result of a batch (maf_nms rows / count):
+ * All three arrays are DEVICE pointers (the NMS result stays on the device).
+ *   rows [B][max_det][row_stride] fp32   columns 0..3 (x1, y1, x2, y2) of the first count[b] rows of image b are rewritten
+ *   params [B][5] fp32                   h0, w0 (source frame), ratio = min(H / h0, W / w0), pad_x = (W - w0 ratio) / 2, pad_y = (H - h0 ratio) / 2
+ *   do_round                             1: round half to even after the clamp (torch.round)
+ * (x - pad) / ratio as an IEEE fp32 divide, clamp to [0, w0] / [0, h0] — the operation order of the reference's tensor ops on the CPU.
+ */
+int maf_rescale_boxes(float* rows, const int32_t* count, int32_t B, int32_t max_det, int32_t row_stride, const float* params,
+                      int32_t do_round, maf_stream_t stream);
+
 /* Diagnostics: shader-clock cycle stamps of image 0 of the last maf_nms call (synchronises the device):
  * [0] sort, [1] kept-list screening, [2] wave resolution, [3] total, [4] candidates, [5] survivors. */
 int maf_nms_debug(uint64_t* host8);

@@ -7,6 +7,7 @@
 //   y    = torch.ops.mafyolo.dwconv_bias_act(x, w, b, act)             # UniRepLKNetBlock after reparameterize (:3085-3100)
 //   pred = torch.ops.mafyolo.head_decode(cls, reg, strides)            # Detect_yaml.forward eval branch (yolov6/models/yolo.py:355-396)
 //   rows, counts = torch.ops.mafyolo.decode_nms(pred, conf, iou, agnostic, multi_label, max_det, classes)   # non_max_suppression (yolov6/utils/nms.py:31-105)
+//   imgs = torch.ops.mafyolo.letterbox(frames, H, W, geometry, color, bgr)   # letterbox + precess_image (data_augment.py:53-82, inferer.py:169-179)
 //
 // Every op takes / returns at::Tensor (NCHW shape, channels_last = NHWC memory, fp16 or fp32, on the HIP device), runs on the CURRENT HIP
 // stream, allocates its outputs through the caching allocator, keeps no reference after it returns and reports errors as RuntimeError
@@ -18,6 +19,7 @@
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
+#include <cstring>
 #include <tuple>
 #include <vector>
 
@@ -363,6 +365,38 @@ std::tuple<Tensor, Tensor, Tensor> bn_act_backward(const Tensor& x_in, const Ten
     return {dx, dg, db};
 }
 
+// frames[b] uint8 [h_b, w_b, 3] (channel stride 1, pixel stride 3, any row pitch: crops and views pass as they are), geometry = B x (new_h, new_w,
+// top, left), color = the border in the frames' channel order -> uint8 [B, 3, H, W] RGB planes (letterbox + precess_image of the reference)
+Tensor letterbox(at::TensorList frames, int64_t H, int64_t W, at::IntArrayRef geometry, at::IntArrayRef color, bool bgr) {
+    const int64_t B = (int64_t)frames.size();
+    TORCH_CHECK(B > 0, "mafyolo::letterbox: empty frame list");
+    const c10::DeviceGuard device_guard(frames[0].device());
+    TORCH_CHECK((int64_t)geometry.size() == 4 * B, "mafyolo::letterbox: geometry holds (new_h, new_w, top, left) per frame");
+    TORCH_CHECK(color.size() == 3, "mafyolo::letterbox: color has 3 entries");
+    std::vector<maf_letterbox_image_t> tab(B);
+    for (int64_t b = 0; b < B; ++b) {
+        const Tensor& f = frames[b];
+        TORCH_CHECK(f.is_cuda() && f.device() == frames[0].device(), "mafyolo::letterbox: frames on one HIP device (there is no CPU path)");
+        TORCH_CHECK(f.scalar_type() == at::kByte && f.dim() == 3 && f.size(2) == 3 && f.stride(2) == 1 && f.stride(1) == 3,
+                    "mafyolo::letterbox: frames are uint8 [h, w, 3] with pixel stride 3 and channel stride 1");
+        tab[b].ptr = f.data_ptr<uint8_t>(); tab[b].pitch = f.size(0) > 1 ? f.stride(0) : 3 * f.size(1);
+        tab[b].h = (int)f.size(0); tab[b].w = (int)f.size(1);
+        tab[b].new_h = (int)geometry[4 * b]; tab[b].new_w = (int)geometry[4 * b + 1]; tab[b].top = (int)geometry[4 * b + 2]; tab[b].left = (int)geometry[4 * b + 3];
+    }
+    const uint8_t col[3] = {(uint8_t)color[0], (uint8_t)color[1], (uint8_t)color[2]};
+    Tensor out = at::empty({B, 3, H, W}, frames[0].options().memory_format(c10::nullopt));
+    Tensor dev_tab;
+    if (B > MAF_LETTERBOX_KARG_MAX) {        // the table goes up on the current stream from pinned memory: no host sync
+        const int64_t bytes = B * (int64_t)sizeof(maf_letterbox_image_t);
+        Tensor host = at::empty({bytes}, at::TensorOptions().dtype(at::kByte).pinned_memory(true));
+        std::memcpy(host.data_ptr(), tab.data(), bytes);
+        dev_tab = host.to(out.device(), /*non_blocking=*/true);
+    }
+    check(maf_letterbox(tab.data(), dev_tab.defined() ? reinterpret_cast<const maf_letterbox_image_t*>(dev_tab.data_ptr()) : nullptr, (int)B, (int)H, (int)W,
+                        col, bgr ? 1 : 0, out.data_ptr<uint8_t>(), stream_of(out)), "letterbox");
+    return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(mafyolo, m) {
@@ -380,6 +414,7 @@ TORCH_LIBRARY(mafyolo, m) {
     m.def("dwconv_wgrad(Tensor x, Tensor dy, int k) -> Tensor");
     m.def("head_decode(Tensor[] cls, Tensor[] reg, float[] strides) -> Tensor");
     m.def("decode_nms(Tensor pred, float conf_thres, float iou_thres, bool agnostic, bool multi_label, int max_det, int[]? classes) -> (Tensor, Tensor)");
+    m.def("letterbox(Tensor[] frames, int H, int W, int[] geometry, int[] color, bool bgr) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(mafyolo, CUDA, m) {       // the HIP device is the "CUDA" dispatch key of PyTorch-ROCm
@@ -397,4 +432,5 @@ TORCH_LIBRARY_IMPL(mafyolo, CUDA, m) {       // the HIP device is the "CUDA" dis
     m.impl("dwconv_wgrad", &dwconv_wgrad);
     m.impl("head_decode", &head_decode);
     m.impl("decode_nms", &decode_nms);
+    m.impl("letterbox", &letterbox);
 }
