@@ -629,6 +629,59 @@ int maf_letterbox(const maf_letterbox_image_t* imgs, const maf_letterbox_image_t
 int maf_rescale_boxes(float* rows, const int32_t* count, int32_t B, int32_t max_det, int32_t row_stride, const float* params,
                       int32_t do_round, maf_stream_t stream);
 
+/*
+ * Training augmentation on the device — replaces the pixel work of TrainValDataset.__getitem__ (yolov6/data/datasets.py:
+ * 147-275) for a batch; the random parameters and the labels are host bookkeeping (maf-yolo_amd/augment.py), the pixel rules are those of
+ * tests/augment_ref.py, bit for bit.
+ *
+ * maf_augment_resize: load_image's cv2.resize INTER_LINEAR (augment mode), n frames in one launch, uint8 HWC in, uint8 HWC out.
+ *   frames [n]    HOST table (validated); frames_dev: DEVICE copy of the same table, read by the kernel (always required)
+ *   src           DEVICE, uint8 HWC (3 channels, pixel stride 3, row pitch src_pitch >= 3 w bytes); reads stay in [row * pitch, + 3 w) of rows < h
+ *   dst           DEVICE, uint8 HWC new_h x new_w, pitch 3 new_w, no alignment needed; every byte written once; must not overlap any src
+ *   The rule of maf_letterbox's resize (tests/letterbox_ref.py): INTER_LINEAR, the exact-2x area-fast average, a copy for equal sizes.
+ */
+typedef struct {
+    const uint8_t* src; int64_t src_pitch;
+    int32_t h, w;                        /* source frame */
+    uint8_t* dst;
+    int32_t new_h, new_w;                /* resized frame, pitch 3 new_w */
+} maf_augment_frame_t;
+int maf_augment_resize(const maf_augment_frame_t* frames, const maf_augment_frame_t* frames_dev, int32_t n, maf_stream_t stream);
+
+/*
+ * maf_mosaic_affine: the uint8 [B, 3, S, S] RGB batch from per-sample parameters, one launch: for every output pixel, the flip index map,
+ * OpenCV's fixed-point warpAffine (INTER_LINEAR, BORDER_CONSTANT 114) of the virtual mosaic canvas — never materialised: a canvas pixel is
+ * read from the tile whose rectangle holds it, 114 elsewhere — the mixup blend with a second warped canvas, uint8 BGR2HSV + three tables +
+ * HSV2BGR, BGR -> RGB.
+ *   samples [B]   HOST table (validated before anything touches the device); samples_dev: DEVICE copy of the same table, read by the kernel
+ *   minv[l]       invertAffineTransform of layer l's M (layer 0: the sample's mosaic; layer 1: the cached mosaic mixed in)
+ *   ntiles[l]     1..MAF_AUGMENT_MAX_TILES tiles for layer 0; 0 (no mixup) or 1..4 for layer 1; r: mixup ratio of layer 0
+ *   tile          ptr: DEVICE uint8 HWC frame (pitch bytes, h x w); canvas [x0, x1) x [y0, y1) reads frame pixel (x + dx, y + dy), which
+ *                 must lie inside the frame (checked); rectangles of one layer do not overlap
+ *   hsv, flipud, fliplr   0 / 1; lut: hue, saturation, value tables (used when hsv = 1)
+ *   S             the output side, a positive multiple of 32
+ *   out           DEVICE, 4-byte aligned, uint8 [B, 3, S, S]: every byte written exactly once (32-bit stores)
+ * maf_augment_sample_size: sizeof(maf_augment_sample_t), for bindings to check their mirror.
+ */
+#define MAF_AUGMENT_MAX_TILES 4
+typedef struct {
+    const uint8_t* ptr; int64_t pitch;
+    int32_t h, w;                        /* frame */
+    int32_t x0, y0, x1, y1;              /* canvas rectangle */
+    int32_t dx, dy;                      /* frame pixel = canvas pixel + (dx, dy) */
+} maf_augment_tile_t;
+typedef struct {
+    double minv[2][6];
+    double r;
+    int32_t ntiles[2];
+    int32_t hsv, flipud, fliplr, reserved;
+    maf_augment_tile_t tile[2][MAF_AUGMENT_MAX_TILES];
+    uint8_t lut[3][256];
+} maf_augment_sample_t;
+int32_t maf_augment_sample_size(void);
+int maf_mosaic_affine(const maf_augment_sample_t* samples, const maf_augment_sample_t* samples_dev, int32_t B, int32_t S, uint8_t* out,
+                      maf_stream_t stream);
+
 /* Diagnostics: shader-clock cycle stamps of image 0 of the last maf_nms call (synchronises the device):
  * [0] sort, [1] kept-list screening, [2] wave resolution, [3] total, [4] candidates, [5] survivors. */
 int maf_nms_debug(uint64_t* host8);

@@ -21,6 +21,7 @@
 // and plane as one 32-bit store (W is a multiple of 32).  Border rows are pure stores.  Every byte of the output is written exactly once;
 // every source read is inside [row * pitch, row * pitch + 3 w) of a row < h.
 #include "maf_common.h"
+#include "resize_linear.h"
 
 #include <algorithm>
 
@@ -37,14 +38,6 @@ struct LbArgs {
     int src_ch[3];                         // output plane p reads source channel src_ch[p]
     maf_letterbox_image_t img[MAF_LETTERBOX_KARG_MAX];
 };
-
-// OpenCV's coefficient sequence for one destination index (resize.cpp: float(... in double ...), cvFloor, fx -= sx)
-__device__ __forceinline__ void lin_coef(int d, double scale, int& s, float& f) {
-    f = (float)(((double)d + 0.5) * scale - 0.5);
-    s = (int)floorf(f);
-    f -= (float)s;
-}
-__device__ __forceinline__ int coef_q(float c) { return (int)rintf(c * 2048.f); }
 
 // stage bytes [0, n) of the source row at `src` into lds + (src & 15): aligned 16-byte chunks fully inside the row as one load each,
 // the (at most two) partial chunks byte by byte

@@ -8,6 +8,7 @@
 //   pred = torch.ops.mafyolo.head_decode(cls, reg, strides)            # Detect_yaml.forward eval branch (yolov6/models/yolo.py:355-396)
 //   rows, counts = torch.ops.mafyolo.decode_nms(pred, conf, iou, agnostic, multi_label, max_det, classes)   # non_max_suppression (yolov6/utils/nms.py:31-105)
 //   imgs = torch.ops.mafyolo.letterbox(frames, H, W, geometry, color, bgr)   # letterbox + precess_image (data_augment.py:53-82, inferer.py:169-179)
+//   imgs = torch.ops.mafyolo.mosaic_affine(samples, samples_dev, S)     # mosaic + random_affine + mixup + augment_hsv + flips (datasets.py:147-275)
 //
 // Every op takes / returns at::Tensor (NCHW shape, channels_last = NHWC memory, fp16 or fp32, on the HIP device), runs on the CURRENT HIP
 // stream, allocates its outputs through the caching allocator, keeps no reference after it returns and reports errors as RuntimeError
@@ -397,6 +398,23 @@ Tensor letterbox(at::TensorList frames, int64_t H, int64_t W, at::IntArrayRef ge
     return out;
 }
 
+// samples: CPU uint8 [B, sizeof(maf_augment_sample_t)] (validated here), samples_dev: its copy on the HIP device (read by the kernel) ->
+// uint8 [B, 3, S, S] RGB.  The tables hold raw device pointers to the frames (maf-yolo_amd/augment.py builds them): the caller keeps those
+// frames alive until the current stream has passed this op.
+Tensor mosaic_affine(const Tensor& samples, const Tensor& samples_dev, int64_t S) {
+    const int64_t sz = (int64_t)sizeof(maf_augment_sample_t);
+    TORCH_CHECK(samples.device().is_cpu() && samples.scalar_type() == at::kByte && samples.is_contiguous() && samples.dim() == 2 && samples.size(1) == sz,
+                "mafyolo::mosaic_affine: samples is a contiguous CPU uint8 [B, ", sz, "] table");
+    TORCH_CHECK(samples_dev.is_cuda() && samples_dev.scalar_type() == at::kByte && samples_dev.is_contiguous() && samples_dev.sizes() == samples.sizes(),
+                "mafyolo::mosaic_affine: samples_dev is the table's contiguous copy on the HIP device (there is no CPU path)");
+    const c10::DeviceGuard device_guard(samples_dev.device());
+    const int64_t B = samples.size(0);
+    Tensor out = at::empty({B, 3, S, S}, samples_dev.options());
+    check(maf_mosaic_affine(reinterpret_cast<const maf_augment_sample_t*>(samples.data_ptr()), reinterpret_cast<const maf_augment_sample_t*>(samples_dev.data_ptr()),
+                            (int)B, (int)S, out.data_ptr<uint8_t>(), stream_of(out)), "mosaic_affine");
+    return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(mafyolo, m) {
@@ -415,6 +433,7 @@ TORCH_LIBRARY(mafyolo, m) {
     m.def("head_decode(Tensor[] cls, Tensor[] reg, float[] strides) -> Tensor");
     m.def("decode_nms(Tensor pred, float conf_thres, float iou_thres, bool agnostic, bool multi_label, int max_det, int[]? classes) -> (Tensor, Tensor)");
     m.def("letterbox(Tensor[] frames, int H, int W, int[] geometry, int[] color, bool bgr) -> Tensor");
+    m.def("mosaic_affine(Tensor samples, Tensor samples_dev, int S) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(mafyolo, CUDA, m) {       // the HIP device is the "CUDA" dispatch key of PyTorch-ROCm
@@ -433,4 +452,5 @@ TORCH_LIBRARY_IMPL(mafyolo, CUDA, m) {       // the HIP device is the "CUDA" dis
     m.impl("head_decode", &head_decode);
     m.impl("decode_nms", &decode_nms);
     m.impl("letterbox", &letterbox);
+    m.impl("mosaic_affine", &mosaic_affine);
 }

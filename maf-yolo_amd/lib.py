@@ -40,6 +40,27 @@ class MafLetterboxImage(C.Structure):
 LETTERBOX_KARG_MAX = 64       # MAF_LETTERBOX_KARG_MAX: frames whose table travels as kernel arguments; larger batches pass a device copy
 
 
+class MafAugmentFrame(C.Structure):
+    """maf_augment_frame_t (include/mafyolo_hip.h): one resize of maf_augment_resize."""
+    _fields_ = [("src", C.c_void_p), ("src_pitch", C.c_int64), ("h", C.c_int32), ("w", C.c_int32),
+                ("dst", C.c_void_p), ("new_h", C.c_int32), ("new_w", C.c_int32)]
+
+
+AUGMENT_MAX_TILES = 4         # MAF_AUGMENT_MAX_TILES
+
+
+class MafAugmentTile(C.Structure):
+    """maf_augment_tile_t: a frame placed on the virtual canvas of maf_mosaic_affine."""
+    _fields_ = [("ptr", C.c_void_p), ("pitch", C.c_int64), ("h", C.c_int32), ("w", C.c_int32),
+                ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32), ("dx", C.c_int32), ("dy", C.c_int32)]
+
+
+class MafAugmentSample(C.Structure):
+    """maf_augment_sample_t: one sample of maf_mosaic_affine (inverse affine per layer, tiles, mixup ratio, flags, HSV tables)."""
+    _fields_ = [("minv", (C.c_double * 6) * 2), ("r", C.c_double), ("ntiles", C.c_int32 * 2), ("hsv", C.c_int32), ("flipud", C.c_int32),
+                ("fliplr", C.c_int32), ("reserved", C.c_int32), ("tile", (MafAugmentTile * AUGMENT_MAX_TILES) * 2), ("lut", (C.c_uint8 * 256) * 3)]
+
+
 class MafEmaDesc(C.Structure):
     """maf_ema_desc_t (include/mafyolo_hip.h): one (average, model) tensor pair of maf_ema_update."""
     _fields_ = [("dst", C.c_void_p), ("src", C.c_void_p), ("total", C.c_int64), ("block0", C.c_int32), ("reserved", C.c_int32)]
@@ -89,6 +110,7 @@ EXPORTS = ["maf_last_error", "maf_version", "maf_op_size", "maf_op_launch", "maf
            "maf_engine_run", "maf_engine_run_filtered", "maf_engine_run_graph", "maf_engine_run_timed", "maf_engine_destroy", "maf_nms_workspace_bytes", "maf_nms", "maf_nms_ex", "maf_nms_debug", "maf_pack_w1x1_bytes", "maf_pack_w1x1", "maf_pack_dw", "maf_pack_batch", "maf_pack_desc_size", "maf_ema_update", "maf_ema_desc_size", "maf_sgd_update", "maf_sgd_desc_size", "maf_nonfinite_check", "maf_range_desc_size", "maf_maxpool_forward", "maf_maxpool_backward", "maf_upsample2x_forward", "maf_upsample2x_backward", "maf_zero", "maf_grad_fold", "maf_add_sub2", "maf_colsum", "maf_dw_wgrad", "maf_dw_wgrad31", "maf_stem_train", "maf_image_to_nhwc8", "maf_bottleneck_record_bytes", "maf_bottleneck_tail_record_bytes", "maf_bottleneck_tail_supported", "maf_conv1dw_record_bytes", "maf_head_tail_record_bytes", "maf_stem2_record_bytes", "maf_conv3s2_lds_record_bytes", "maf_mprep_lds_record_bytes", "maf_mprep_wreg_record_bytes", "maf_conv3s2_wreg_record_bytes", "maf_conv1x1_stats_supported", "maf_coco_rows", "maf_conv1x1_wgrad", "maf_conv_wgrad", "maf_bn_forward", "maf_bn_backward", "maf_bn_backward_acc", "maf_set_deterministic", "maf_dw_branches", "maf_dw_branches_stats", "maf_bn_forward_ex", "maf_bn_replicas", "maf_bn_stats", "maf_bn_sum_forward", "maf_bn_sum_forward_stats", "maf_bn_sum_backward", "maf_tal_targets", "maf_tal_assign", "maf_atss_assign", "maf_loss_partial_rows", "maf_loss_decode", "maf_loss_terms",
            "maf_detect_join", "maf_detect_join_backward", "maf_nhwc_sum", "maf_stream_fork", "maf_stream_join", "maf_tape_fn_id", "maf_tape_fn_nargs", "maf_tape_rec_size", "maf_tape_run", "maf_tape_toggle",
            "maf_stream_create_masked", "maf_stream_destroy", "maf_letterbox", "maf_letterbox_lds_bytes", "maf_rescale_boxes",
+           "maf_augment_resize", "maf_mosaic_affine", "maf_augment_sample_size",
            "maf_timer_create", "maf_timer_start", "maf_timer_stop", "maf_timer_elapsed_ms", "maf_timer_destroy"]
 
 _lib = None
@@ -234,6 +256,11 @@ def load():
     lib.maf_letterbox_lds_bytes.argtypes = [C.POINTER(MafLetterboxImage), C.c_int32, C.c_int32]
     lib.maf_letterbox_lds_bytes.restype = C.c_int64
     lib.maf_rescale_boxes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.maf_augment_resize.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.maf_mosaic_affine.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.maf_augment_sample_size.restype = C.c_int32
+    if lib.maf_augment_sample_size() != C.sizeof(MafAugmentSample):
+        raise MafError("libmafyolo_hip.so was built for a maf_augment_sample_t of %d bytes, this binding declares %d: rebuild" % (lib.maf_augment_sample_size(), C.sizeof(MafAugmentSample)))
     lib.maf_timer_create.argtypes = [C.POINTER(C.c_void_p)]
     lib.maf_timer_start.argtypes = [C.c_void_p, C.c_void_p]
     lib.maf_timer_stop.argtypes = [C.c_void_p, C.c_void_p]

@@ -8,6 +8,7 @@
     pred = ops.head_decode(cls, reg, [8., 16., 32.])               # Detect_yaml eval branch (yolov6/models/yolo.py:355-396)
     rows, counts = ops.decode_nms(pred, 0.03, 0.65, False, True, 300, None)     # non_max_suppression (yolov6/utils/nms.py:31-105)
     imgs = ops.letterbox(frames, H, W, geometry, [114] * 3, True)  # letterbox + precess_image (data_augment.py:53-82); maf_yolo_amd.letterbox
+    imgs = ops.mosaic_affine(samples, samples_dev, 640)            # the pixels of TrainValDataset.__getitem__ (datasets.py:147-275); maf_yolo_amd.train_batch
     dets = torch_ops.non_max_suppression(pred, 0.03, 0.65, multi_label=True)    # ... as the reference's list of [n_i, 6] tensors
 
 The C++ side (csrc/torch_ops.cpp) defines the schemas and the HIP ("CUDA" dispatch key) implementations, which marshal at::Tensor into
@@ -28,7 +29,7 @@ from . import lib
 ACT_NONE, ACT_RELU, ACT_SILU, ACT_SIGMOID = lib.ACT_NONE, lib.ACT_RELU, lib.ACT_SILU, lib.ACT_SIGMOID
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libmafyolo_torch.so")
 OPS = ("conv1x1_bias_act", "conv3x3s2_bias_act", "dwconv_bias_act", "conv1x1_dgrad", "conv3x3s2_dgrad", "conv_wgrad", "dwconv_dgrad", "dwconv_wgrad",
-       "head_decode", "decode_nms", "mprep", "sppf", "bn_act", "bn_act_backward", "letterbox")
+       "head_decode", "decode_nms", "mprep", "sppf", "bn_act", "bn_act_backward", "letterbox", "mosaic_affine")
 _registered = False
 
 
@@ -89,6 +90,10 @@ def _register():
     @L.register_fake("mafyolo::letterbox")
     def _(frames, H, W, geometry, color, bgr):
         return frames[0].new_empty((len(frames), 3, H, W), dtype=torch.uint8)
+
+    @L.register_fake("mafyolo::mosaic_affine")
+    def _(samples, samples_dev, S):
+        return samples_dev.new_empty((samples.shape[0], 3, S, S), dtype=torch.uint8)
 
     @L.register_fake("mafyolo::mprep")
     def _(x, w1, b1, w3, b3):
