@@ -682,6 +682,55 @@ int32_t maf_augment_sample_size(void);
 int maf_mosaic_affine(const maf_augment_sample_t* samples, const maf_augment_sample_t* samples_dev, int32_t B, int32_t S, uint8_t* out,
                       maf_stream_t stream);
 
+/*
+ * In-process precision / recall / mAP of an evaluation (the do_pr_metric path of Evaler.predict_model, yolov6/core/evaler.py:195-268, with
+ * yolov6/utils/metrics.py process_batch, ConfusionMatrix, ap_per_class, compute_ap); the rules are those of tests/pr_metric_ref.py.
+ * Every pointer below is a DEVICE pointer; nothing synchronises the host.
+ *
+ * state [maf_pr_state_ints(nc)] int32, zeroed by the caller before the first batch: [0] error bits (MAF_PR_ERR_*), [1] 1 once any row
+ *   is correct at any threshold, [2, 2 + nc) labels per class, [2 + nc, 2 + 2 nc) predictions per class, then the confusion matrix
+ *   [nc + 1][nc + 1] (row: detected class, column: true class; index nc = background).
+ *
+ * maf_pr_match: one batch, one workgroup per image.
+ *   rows [B][max_det][6] fp32, count [B] int32   the maf_nms result (letterboxed xyxy, conf, cls); max_det <= MAF_PR_MAX_DET
+ *   targets [n_targets][6] fp32                  image index in the batch, class, x, y, w, h normalised to the letterboxed H x W, in any
+ *                                                image order (order within an image is kept); flags & MAF_PR_LABELS_XYXY: class, x1, y1,
+ *                                                x2, y2 in native pixels and no rescale of labels or detections (img_params unused)
+ *   img_params [B][6] fp32                       maf_coco_rows' image parameters (h0, w0, gain x, gain y, pad w, pad h)
+ *   iouv [niou] fp32, niou <= 16                 thresholds, compared with >=
+ *   flags & MAF_PR_CONFUSION                     update the confusion matrix (detections with conf > cm_conf, iou > cm_iou, fp32)
+ *   offs_in [1] int64                            record index of this batch's first detection; offs_out [1] := offs_in + rows of the batch
+ *   keys, masks [capacity]                       per detection (at offs_in + rows of earlier images + row): key = class << 32 | the
+ *                                                descending-order bits of conf; mask bit t = correct at iouv[t].  Slots never written keep
+ *                                                the caller's fill (INT64_MAX for keys).
+ *   Device-side errors (a class outside [0, nc) or not integral, more than MAF_PR_MAX_LABELS labels in an image, records past capacity)
+ *   set bits of state[0]; the launch itself succeeds.
+ *
+ * maf_pr_curves: once per evaluation, on the keys sorted ascending by a STABLE sort (sorted_keys, perm = the sort's indices into keys /
+ *   masks): per-class offsets, then one workgroup per (class, threshold), then the summary.  workspace: maf_pr_workspace_bytes(nc, niou,
+ *   capacity) bytes.  out [maf_pr_out_doubles(nc, niou)] fp64: header [MAF_PR_HEADER] (F1 index, mp, mr, mf1, map50, map, classes with
+ *   labels, any correct, error bits), then p, r, f1, py [nc][1000], ap [nc][niou], labels per class [nc], confusion [(nc+1)^2].  Rows of
+ *   classes without labels are not summarised (callers keep the rows with labels > 0: np.unique of the target classes).
+ */
+#define MAF_PR_MAX_DET 1024
+#define MAF_PR_MAX_LABELS 1024
+#define MAF_PR_MAX_CLASSES 1024
+#define MAF_PR_HEADER 16
+#define MAF_PR_LABELS_XYXY 1
+#define MAF_PR_CONFUSION 2
+#define MAF_PR_ERR_CLASS 1
+#define MAF_PR_ERR_LABELS 2
+#define MAF_PR_ERR_CAPACITY 4
+int64_t maf_pr_state_ints(int32_t nc);
+int64_t maf_pr_out_doubles(int32_t nc, int32_t niou);
+int64_t maf_pr_workspace_bytes(int32_t nc, int32_t niou, int64_t capacity);
+int maf_pr_match(const float* rows, const int32_t* count, int32_t B, int32_t max_det, const float* targets, int32_t n_targets,
+                 const float* img_params, int32_t H, int32_t W, const float* iouv, int32_t niou, int32_t nc, int32_t flags,
+                 float cm_conf, float cm_iou, const int64_t* offs_in, int64_t* offs_out, int64_t* keys, uint16_t* masks,
+                 int64_t capacity, int32_t* state, maf_stream_t stream);
+int maf_pr_curves(const int64_t* sorted_keys, const int64_t* perm, const uint16_t* masks, int64_t capacity, const int32_t* state,
+                  int32_t nc, int32_t niou, void* workspace, int64_t workspace_bytes, double* out, maf_stream_t stream);
+
 /* Diagnostics: shader-clock cycle stamps of image 0 of the last maf_nms call (synchronises the device):
  * [0] sort, [1] kept-list screening, [2] wave resolution, [3] total, [4] candidates, [5] survivors. */
 int maf_nms_debug(uint64_t* host8);

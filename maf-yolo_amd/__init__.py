@@ -8,6 +8,8 @@ from .nms import non_max_suppression, non_max_suppression_async, nms_raw  # noqa
 from .post import convert_to_coco_format, coco_rows  # noqa: F401
 from .letterbox import letterbox, eval_batch, rescale_boxes, detect_frames  # noqa: F401
 from .augment import TrainAugment, train_batch  # noqa: F401
+from . import metrics  # noqa: F401
+from .metrics import PrMetric  # noqa: F401
 from .checkpoint import load_checkpoint, reference_state_dict  # noqa: F401
 from .loss import ComputeLoss, task_aligned_assign  # noqa: F401
 from .streams import concurrent_streams  # noqa: F401

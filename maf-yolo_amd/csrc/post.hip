@@ -7,6 +7,7 @@
 // (subtract pad, IEEE divide by the gain, clamp, centre/extent, centre - extent/2), so the rows are bit-identical; the decimal
 // rounding of :425-426 stays on the host (maf-yolo_amd/post.py), where it is one vectorised numpy call.
 #include "maf_common.h"
+#include "scale_coords.h"
 
 namespace {
 
@@ -22,13 +23,10 @@ __global__ __launch_bounds__(256) void coco_rows_kernel(const PostArgs a) {
     for (int i = 0; i < b; ++i) base += min(a.count[i], a.max_det);
     const int n = min(a.count[b], a.max_det);
     if (b == a.B - 1 && threadIdx.x == 0) *a.total = base + n;
-    const float h0 = a.img[b * 6 + 0], w0 = a.img[b * 6 + 1], gx = a.img[b * 6 + 2], gy = a.img[b * 6 + 3];
-    const float pw = a.img[b * 6 + 4], ph = a.img[b * 6 + 5];
     for (int k = threadIdx.x; k < n; k += blockDim.x) {
         const float* r = a.rows + ((size_t)b * a.max_det + k) * 6;
-        float x1 = (r[0] - pw) / gx, y1 = (r[1] - ph) / gy, x2 = (r[2] - pw) / gx, y2 = (r[3] - ph) / gy;
-        x1 = fminf(fmaxf(x1, 0.f), w0); x2 = fminf(fmaxf(x2, 0.f), w0);
-        y1 = fminf(fmaxf(y1, 0.f), h0); y2 = fminf(fmaxf(y2, 0.f), h0);
+        float x1 = r[0], y1 = r[1], x2 = r[2], y2 = r[3];
+        maf_scale_box(x1, y1, x2, y2, a.img + b * 6);
         const float cx = (x1 + x2) / 2.f, cy = (y1 + y2) / 2.f, w = x2 - x1, h = y2 - y1;
         const int cls = (int)r[5];
         float* o = a.out + (size_t)(base + k) * 7;

@@ -9,6 +9,8 @@
 //   rows, counts = torch.ops.mafyolo.decode_nms(pred, conf, iou, agnostic, multi_label, max_det, classes)   # non_max_suppression (yolov6/utils/nms.py:31-105)
 //   imgs = torch.ops.mafyolo.letterbox(frames, H, W, geometry, color, bgr)   # letterbox + precess_image (data_augment.py:53-82, inferer.py:169-179)
 //   imgs = torch.ops.mafyolo.mosaic_affine(samples, samples_dev, S)     # mosaic + random_affine + mixup + augment_hsv + flips (datasets.py:147-275)
+//   torch.ops.mafyolo.pr_match(rows, count, targets, img, H, W, iouv, nc, flags, cm_conf, cm_iou, offs, i, keys, masks, state)  # evaler.py:195-238
+//   out = torch.ops.mafyolo.pr_curves(keys, masks, state, nc, niou)    # ap_per_class + the summary of evaler.py:240-268 (metrics.py:13-103)
 //
 // Every op takes / returns at::Tensor (NCHW shape, channels_last = NHWC memory, fp16 or fp32, on the HIP device), runs on the CURRENT HIP
 // stream, allocates its outputs through the caching allocator, keeps no reference after it returns and reports errors as RuntimeError
@@ -415,6 +417,47 @@ Tensor mosaic_affine(const Tensor& samples, const Tensor& samples_dev, int64_t S
     return out;
 }
 
+// One batch of the in-process mAP statistics (maf_pr_match): rows / count are the maf_nms result, targets fp32 [N, 6], img_params fp32 [B, 6]
+// (maf_coco_rows' parameters; ignored with MAF_PR_LABELS_XYXY), iouv fp32 [niou].  offs int64: offs[batch] is read, offs[batch + 1] written;
+// keys int64 / masks int16 [capacity] and state int32 [maf_pr_state_ints(nc)] are updated in place (maf-yolo_amd/metrics.py owns them).
+void pr_match(const Tensor& rows, const Tensor& count, const Tensor& targets, const Tensor& img_params, int64_t H, int64_t W, const Tensor& iouv,
+              int64_t nc, int64_t flags, double cm_conf, double cm_iou, const Tensor& offs, int64_t batch, const Tensor& keys, const Tensor& masks,
+              const Tensor& state) {
+    for (const Tensor* t : {&rows, &count, &targets, &img_params, &iouv, &offs, &keys, &masks, &state})
+        TORCH_CHECK(t->is_cuda() && t->is_contiguous(), "mafyolo::pr_match: every tensor is a contiguous HIP tensor (there is no CPU path)");
+    TORCH_CHECK(rows.scalar_type() == at::kFloat && rows.dim() == 3 && rows.size(2) == 6 && count.scalar_type() == at::kInt && count.numel() == rows.size(0),
+                "mafyolo::pr_match: rows fp32 [B, max_det, 6], count int32 [B]");
+    TORCH_CHECK(targets.scalar_type() == at::kFloat && targets.dim() == 2 && targets.size(1) == 6 && img_params.scalar_type() == at::kFloat &&
+                iouv.scalar_type() == at::kFloat, "mafyolo::pr_match: targets fp32 [N, 6], img_params and iouv fp32");
+    TORCH_CHECK(offs.scalar_type() == at::kLong && batch >= 0 && batch + 1 < offs.numel() && keys.scalar_type() == at::kLong &&
+                masks.scalar_type() == at::kShort && masks.numel() == keys.numel() && state.scalar_type() == at::kInt &&
+                state.numel() == maf_pr_state_ints((int)nc), "mafyolo::pr_match: offs int64, keys int64 / masks int16 [capacity], state int32");
+    const c10::DeviceGuard device_guard(rows.device());
+    check(maf_pr_match(rows.data_ptr<float>(), count.data_ptr<int32_t>(), (int)rows.size(0), (int)rows.size(1), targets.data_ptr<float>(),
+                       (int)targets.size(0), img_params.data_ptr<float>(), (int)H, (int)W, iouv.data_ptr<float>(), (int)iouv.numel(), (int)nc,
+                       (int)flags, (float)cm_conf, (float)cm_iou, offs.data_ptr<int64_t>() + batch, offs.data_ptr<int64_t>() + batch + 1,
+                       keys.data_ptr<int64_t>(), reinterpret_cast<uint16_t*>(masks.data_ptr<int16_t>()), keys.numel(), state.data_ptr<int32_t>(),
+                       stream_of(rows)), "pr_match");
+}
+
+// The curves and the summary (maf_pr_curves) of the records pr_match wrote: one stable sort of the keys on the device, then the HIP launches
+// -> fp64 [maf_pr_out_doubles(nc, niou)] (layout in include/mafyolo_hip.h).
+Tensor pr_curves(const Tensor& keys, const Tensor& masks, const Tensor& state, int64_t nc, int64_t niou) {
+    for (const Tensor* t : {&keys, &masks, &state})
+        TORCH_CHECK(t->is_cuda() && t->is_contiguous(), "mafyolo::pr_curves: every tensor is a contiguous HIP tensor (there is no CPU path)");
+    TORCH_CHECK(keys.scalar_type() == at::kLong && masks.scalar_type() == at::kShort && masks.numel() == keys.numel() && state.scalar_type() == at::kInt &&
+                state.numel() == maf_pr_state_ints((int)nc), "mafyolo::pr_curves: keys int64 / masks int16 [capacity], state int32");
+    const c10::DeviceGuard device_guard(keys.device());
+    auto sorted = keys.sort(/*stable=*/true, /*dim=*/0, /*descending=*/false);
+    const int64_t cap = keys.numel();
+    const int64_t wsb = maf_pr_workspace_bytes((int)nc, (int)niou, cap);
+    Tensor ws = at::empty({wsb}, keys.options().dtype(at::kByte));
+    Tensor out = at::empty({maf_pr_out_doubles((int)nc, (int)niou)}, keys.options().dtype(at::kDouble));
+    check(maf_pr_curves(std::get<0>(sorted).data_ptr<int64_t>(), std::get<1>(sorted).data_ptr<int64_t>(), reinterpret_cast<const uint16_t*>(masks.data_ptr<int16_t>()),
+                        cap, state.data_ptr<int32_t>(), (int)nc, (int)niou, ws.data_ptr(), wsb, out.data_ptr<double>(), stream_of(keys)), "pr_curves");
+    return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(mafyolo, m) {
@@ -434,6 +477,9 @@ TORCH_LIBRARY(mafyolo, m) {
     m.def("decode_nms(Tensor pred, float conf_thres, float iou_thres, bool agnostic, bool multi_label, int max_det, int[]? classes) -> (Tensor, Tensor)");
     m.def("letterbox(Tensor[] frames, int H, int W, int[] geometry, int[] color, bool bgr) -> Tensor");
     m.def("mosaic_affine(Tensor samples, Tensor samples_dev, int S) -> Tensor");
+    m.def("pr_match(Tensor rows, Tensor count, Tensor targets, Tensor img_params, int H, int W, Tensor iouv, int nc, int flags, float cm_conf, "
+          "float cm_iou, Tensor(a!) offs, int batch, Tensor(b!) keys, Tensor(c!) masks, Tensor(d!) state) -> ()");
+    m.def("pr_curves(Tensor keys, Tensor masks, Tensor state, int nc, int niou) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(mafyolo, CUDA, m) {       // the HIP device is the "CUDA" dispatch key of PyTorch-ROCm
@@ -453,4 +499,6 @@ TORCH_LIBRARY_IMPL(mafyolo, CUDA, m) {       // the HIP device is the "CUDA" dis
     m.impl("decode_nms", &decode_nms);
     m.impl("letterbox", &letterbox);
     m.impl("mosaic_affine", &mosaic_affine);
+    m.impl("pr_match", &pr_match);
+    m.impl("pr_curves", &pr_curves);
 }

@@ -7,6 +7,11 @@
     pred_results = loop.predict_model(dataloader)        # list of {"image_id", "category_id", "bbox", "score"} (evaler.py:411-434)
     loop.eval_speed()                                    # {"pre-process": ms, "inference": ms, "NMS": ms} per image, like the reference logs
 
+do_pr_metric=True adds the reference's in-process precision / recall / mAP (evaler.py:143-151, 182-238, 240-271; on by default in its
+tools/eval.py) over metrics.PrMetric: each batch's NMS result and the loader's targets feed one HIP launch, and after the loop
+`loop.pr_metric_result == (map50, map)` as on the reference's Evaler, `loop.pr_metric` holds the full result (p, r, f1, ap, ap_class, py,
+nt, the confusion matrix when plot_confusion_matrix=True; drawing stays the caller's).  The returned COCO rows are the same either way.
+
 Differences from the reference, all inside the same call sequence: `/255` is folded into the first kernel (uint8 images go to the engine as
 they are: fold_preprocess=True; False converts like evaler.py:161-163), the NMS result stays on the device and the COCO rows of a batch are
 one kernel + one device->host copy (post.py).  Everything else — data loader, COCOeval, plots — is the caller's, unchanged.
@@ -15,6 +20,7 @@ import time
 
 import torch
 
+from . import metrics as _metrics
 from . import nms as _nms
 from . import post as _post
 
@@ -25,8 +31,11 @@ def _time_sync(dev):
 
 
 class EvalLoop:
-    def __init__(self, model, conf_thres=0.03, iou_thres=0.65, half=True, ids=None, is_coco=True, scale_exact=False, fold_preprocess=True, device=None):
+    def __init__(self, model, conf_thres=0.03, iou_thres=0.65, half=True, ids=None, is_coco=True, scale_exact=False, fold_preprocess=True, device=None,
+                 do_pr_metric=False, plot_confusion_matrix=False):
         self.model = model.eval()
+        self.do_pr_metric, self.plot_confusion_matrix = do_pr_metric, plot_confusion_matrix
+        self.pr_metric, self.pr_metric_result = None, None
         self.conf_thres, self.iou_thres, self.half = conf_thres, iou_thres, half           # tools/eval.py:29-30 defaults
         self.ids, self.is_coco, self.scale_exact = ids, is_coco, scale_exact
         self.fold_preprocess = fold_preprocess
@@ -40,6 +49,7 @@ class EvalLoop:
     def predict_model(self, dataloader):
         pred_results = []
         dev = self.device
+        metric = _metrics.PrMetric(self.model.nc, confusion=self.plot_confusion_matrix) if self.do_pr_metric else None
         for imgs, targets, paths, shapes in dataloader:
             # pre-process (evaler.py:160-164)
             t1 = _time_sync(dev)
@@ -60,8 +70,13 @@ class EvalLoop:
             raw = _nms.nms_raw(outputs, self.conf_thres, self.iou_thres, multi_label=True)
             self.speed_result[3] += _time_sync(dev) - t3
             self.speed_result[0] += imgs.shape[0]
+            if metric is not None:                          # statistics per image (:195-238), queued behind the NMS: no host sync
+                metric.update(raw[0], raw[2], targets.to(dev, non_blocking=True), imgs.shape[2:], shapes, self.scale_exact)
             # save result (:187)
             pred_results.extend(_post.convert_to_coco_format(raw, imgs, paths, shapes, self.ids, self.is_coco, self.scale_exact))
+        if metric is not None:                              # :240-268
+            self.pr_metric = metric.compute()
+            self.pr_metric_result = self.pr_metric.pr_metric_result
         return pred_results
 
     def eval_speed(self):

@@ -61,6 +61,14 @@ class MafAugmentSample(C.Structure):
                 ("fliplr", C.c_int32), ("reserved", C.c_int32), ("tile", (MafAugmentTile * AUGMENT_MAX_TILES) * 2), ("lut", (C.c_uint8 * 256) * 3)]
 
 
+PR_MAX_DET = 1024             # MAF_PR_MAX_DET / MAF_PR_MAX_LABELS / MAF_PR_MAX_CLASSES: bounds of maf_pr_match / maf_pr_curves
+PR_MAX_LABELS = 1024
+PR_MAX_CLASSES = 1024
+PR_HEADER = 16                # MAF_PR_HEADER: fp64 summary slots at the start of maf_pr_curves' output
+PR_LABELS_XYXY, PR_CONFUSION = 1, 2
+PR_ERR_CLASS, PR_ERR_LABELS, PR_ERR_CAPACITY = 1, 2, 4
+
+
 class MafEmaDesc(C.Structure):
     """maf_ema_desc_t (include/mafyolo_hip.h): one (average, model) tensor pair of maf_ema_update."""
     _fields_ = [("dst", C.c_void_p), ("src", C.c_void_p), ("total", C.c_int64), ("block0", C.c_int32), ("reserved", C.c_int32)]
@@ -111,6 +119,7 @@ EXPORTS = ["maf_last_error", "maf_version", "maf_op_size", "maf_op_launch", "maf
            "maf_detect_join", "maf_detect_join_backward", "maf_nhwc_sum", "maf_stream_fork", "maf_stream_join", "maf_tape_fn_id", "maf_tape_fn_nargs", "maf_tape_rec_size", "maf_tape_run", "maf_tape_toggle",
            "maf_stream_create_masked", "maf_stream_destroy", "maf_letterbox", "maf_letterbox_lds_bytes", "maf_rescale_boxes",
            "maf_augment_resize", "maf_mosaic_affine", "maf_augment_sample_size",
+           "maf_pr_state_ints", "maf_pr_out_doubles", "maf_pr_workspace_bytes", "maf_pr_match", "maf_pr_curves",
            "maf_timer_create", "maf_timer_start", "maf_timer_stop", "maf_timer_elapsed_ms", "maf_timer_destroy"]
 
 _lib = None
@@ -261,6 +270,17 @@ def load():
     lib.maf_augment_sample_size.restype = C.c_int32
     if lib.maf_augment_sample_size() != C.sizeof(MafAugmentSample):
         raise MafError("libmafyolo_hip.so was built for a maf_augment_sample_t of %d bytes, this binding declares %d: rebuild" % (lib.maf_augment_sample_size(), C.sizeof(MafAugmentSample)))
+    lib.maf_pr_state_ints.argtypes = [C.c_int32]
+    lib.maf_pr_state_ints.restype = C.c_int64
+    lib.maf_pr_out_doubles.argtypes = [C.c_int32, C.c_int32]
+    lib.maf_pr_out_doubles.restype = C.c_int64
+    lib.maf_pr_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int64]
+    lib.maf_pr_workspace_bytes.restype = C.c_int64
+    lib.maf_pr_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                 C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.maf_pr_curves.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                  C.c_void_p, C.c_void_p]
     lib.maf_timer_create.argtypes = [C.POINTER(C.c_void_p)]
     lib.maf_timer_start.argtypes = [C.c_void_p, C.c_void_p]
     lib.maf_timer_stop.argtypes = [C.c_void_p, C.c_void_p]

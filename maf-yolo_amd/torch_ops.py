@@ -9,6 +9,8 @@
     rows, counts = ops.decode_nms(pred, 0.03, 0.65, False, True, 300, None)     # non_max_suppression (yolov6/utils/nms.py:31-105)
     imgs = ops.letterbox(frames, H, W, geometry, [114] * 3, True)  # letterbox + precess_image (data_augment.py:53-82); maf_yolo_amd.letterbox
     imgs = ops.mosaic_affine(samples, samples_dev, 640)            # the pixels of TrainValDataset.__getitem__ (datasets.py:147-275); maf_yolo_amd.train_batch
+    ops.pr_match(rows, count, targets, img, H, W, iouv, nc, flags, 0.25, 0.45, offs, i, keys, masks, state)  # evaler.py:195-238; metrics.PrMetric.update
+    out = ops.pr_curves(keys, masks, state, nc, niou)               # ap_per_class + the summary (evaler.py:240-268); metrics.PrMetric.compute
     dets = torch_ops.non_max_suppression(pred, 0.03, 0.65, multi_label=True)    # ... as the reference's list of [n_i, 6] tensors
 
 The C++ side (csrc/torch_ops.cpp) defines the schemas and the HIP ("CUDA" dispatch key) implementations, which marshal at::Tensor into
@@ -29,7 +31,8 @@ from . import lib
 ACT_NONE, ACT_RELU, ACT_SILU, ACT_SIGMOID = lib.ACT_NONE, lib.ACT_RELU, lib.ACT_SILU, lib.ACT_SIGMOID
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libmafyolo_torch.so")
 OPS = ("conv1x1_bias_act", "conv3x3s2_bias_act", "dwconv_bias_act", "conv1x1_dgrad", "conv3x3s2_dgrad", "conv_wgrad", "dwconv_dgrad", "dwconv_wgrad",
-       "head_decode", "decode_nms", "mprep", "sppf", "bn_act", "bn_act_backward", "letterbox", "mosaic_affine")
+       "head_decode", "decode_nms", "mprep", "sppf", "bn_act", "bn_act_backward", "letterbox", "mosaic_affine",
+       "pr_match", "pr_curves")
 _registered = False
 
 
@@ -94,6 +97,14 @@ def _register():
     @L.register_fake("mafyolo::mosaic_affine")
     def _(samples, samples_dev, S):
         return samples_dev.new_empty((samples.shape[0], 3, S, S), dtype=torch.uint8)
+
+    @L.register_fake("mafyolo::pr_match")
+    def _(rows, count, targets, img_params, H, W, iouv, nc, flags, cm_conf, cm_iou, offs, batch, keys, masks, state):
+        return None
+
+    @L.register_fake("mafyolo::pr_curves")
+    def _(keys, masks, state, nc, niou):
+        return keys.new_empty((lib.PR_HEADER + 4000 * nc + nc * niou + nc + (nc + 1) ** 2,), dtype=torch.float64)
 
     @L.register_fake("mafyolo::mprep")
     def _(x, w1, b1, w3, b3):
