@@ -26,6 +26,11 @@ from . import tuner as _tuner, plan_report as _report
 _TORCH_DT = {lib.F16: torch.float16, lib.F32: torch.float32}
 
 
+def _raw(*ts):
+    """The fp32 CPU weights a packer consumed (op record entry `raw`: what a test restates the op from)."""
+    return tuple(t.detach().float().cpu() for t in ts)
+
+
 class Buf:
     """A real NHWC buffer in the arena."""
 
@@ -167,7 +172,7 @@ class Plan:
 
     def _dw(self, name, w, b, src, out, act):
         assert len(src.segs) == 1 and src.segs[0].mode == lib.SRC_DIRECT
-        self._ops.append(dict(kind=lib.OP_DWCONV, name=name, act=act, H=src.H, W=src.W, Cin=src.C, Cout=src.C, ksize=w.shape[-1],
+        self._ops.append(dict(kind=lib.OP_DWCONV, name=name, act=act, H=src.H, W=src.W, Cin=src.C, Cout=src.C, ksize=w.shape[-1], raw=(w.detach().float().cpu(), b.detach().float().cpu()),
                               segs=src.segs, out=out, out_coff=0, w=self._wput(pack.pack_dw(w, self.dtype)),
                               b=self._wput(b.float().cpu()),
                               # operands of the matrix-core variant (aux[0]) and of the pixel-pair variant (aux[1]: csrc/dwconv_p2.hip)
@@ -210,7 +215,7 @@ class Plan:
                     continue
                 out = self._alloc(self.Hin // 4, self.Win // 4, node.cout)
                 self._ops.append(dict(kind=lib.OP_STEM2, name="backbone.0+1", act=lib.ACT_RELU, H=out.H, W=out.W, Hin=self.Hin, Win=self.Win,
-                                      Cin=3, Cout=node.cout, ksize=c0, segs=[], out=out, out_coff=0,
+                                      Cin=3, Cout=node.cout, ksize=c0, segs=[], out=out, out_coff=0, raw=_raw(w0, b0, w, b),
                                       w=self._wput(pack.pack_stem2(w0, b0, w, b)), b=0))
                 y.append(TV([Seg(out, node.cout)], out.H, out.W))
             elif node.kind == "repvgg":
@@ -253,7 +258,7 @@ class Plan:
                     w0, b0, c0, w1_, b1_, c1 = self._stem3
                     w3, b3 = m.conv1.fused()
                     self._ops.append(dict(kind=lib.OP_STEM2, name="backbone.0+1+2.conv1", act=lib.ACT_RELU, H=x.H, W=x.W, Hin=self.Hin, Win=self.Win,
-                                          Cin=3, Cout=c1, ksize=c0, c3=w3.shape[0], segs=[], out=slot[0][0], out_coff=0,
+                                          Cin=3, Cout=c1, ksize=c0, c3=w3.shape[0], segs=[], out=slot[0][0], out_coff=0, raw=_raw(w0, b0, w1_, b1_, w3, b3),
                                           w=self._wput(pack.pack_stem2(w0, b0, w1_, b1_, w3, b3)), b=0))
                     if split:
                         self._ops[-1]["out2"] = slot[1][0]
@@ -271,7 +276,8 @@ class Plan:
                         out = self._alloc(x.H, x.W, node.cout)
                         self._ops.append(dict(kind=lib.OP_BOTTLENECK, name=q + "+conv2", act=lib.ACT_SILU, H=x.H, W=x.W, Cin=c_, Cout=c_, ksize=kl, mid=mid,
                                               segs=[Seg(ib, c_, ic)] + [Seg(slot[j][0], c_, slot[j][1]) for j in range(depth)], out=out, out_coff=0, pt=16, ct=16, tk=nmb,
-                                              tail_c3=node.cout, w=self._wput(rec), b=self._wput(b2p), aux=[self._wput(pack.pack_bottleneck_tail(w3, b3, c_, depth + 1))]))
+                                              tail_c3=node.cout, raw=_raw(*blk.conv1.fused(), *blk.conv2.fused(), *blk.one_conv.fused(), w3, b3),
+                                              w=self._wput(rec), b=self._wput(b2p), aux=[self._wput(pack.pack_bottleneck_tail(w3, b3, c_, depth + 1))]))
                         continue
                     (ob, oc) = slot[d + 2]
                     if mode == 2:
@@ -279,7 +285,7 @@ class Plan:
                         rec, nmb = pack.pack_conv1dw(*blk.conv1.fused(), *blk.conv2.fused())
                         t2 = self._alloc(x.H, x.W, mid)
                         self._ops.append(dict(kind=lib.OP_CONV1DW, name=q + ".conv1dw", act=lib.ACT_SILU, H=x.H, W=x.W, Cin=c_, Cout=mid,
-                                              ksize=blk.conv2.dwconv.kernel_size, segs=[Seg(ib, c_, ic)], out=t2, out_coff=0, w=self._wput(rec),
+                                              ksize=blk.conv2.dwconv.kernel_size, segs=[Seg(ib, c_, ic)], out=t2, out_coff=0, raw=_raw(*blk.conv1.fused(), *blk.conv2.fused()), w=self._wput(rec),
                                               b=self._wput(torch.zeros(8))))
                         self._conv1x1(q + ".one_conv", *blk.one_conv.fused(), TV([Seg(t2, mid)], x.H, x.W), ob, oc, lib.ACT_SILU)
                         continue
@@ -289,7 +295,7 @@ class Plan:
                         k = blk.conv2.dwconv.kernel_size
                         th, tw = 16, 16                                   # fixed by the MFMA shapes of csrc/bottleneck.hip
                         self._ops.append(dict(kind=lib.OP_BOTTLENECK, name=q, act=lib.ACT_SILU, H=x.H, W=x.W, Cin=c_, Cout=c_, ksize=k, mid=mid,
-                                              segs=[Seg(ib, c_, ic)], out=ob, out_coff=oc, pt=th, ct=tw, tk=nmb,
+                                              segs=[Seg(ib, c_, ic)], out=ob, out_coff=oc, pt=th, ct=tw, tk=nmb, raw=_raw(*blk.conv1.fused(), *blk.conv2.fused(), *blk.one_conv.fused()),
                                               w=self._wput(rec), b=self._wput(b2p), aux=[]))
                         continue
                     t1, t2 = self._alloc(x.H, x.W, mid), self._alloc(x.H, x.W, mid)
@@ -337,7 +343,7 @@ class Plan:
                 cat = self._alloc(x.H, x.W, 4 * c_)
                 self._conv1x1(p + ".cv1", *m.cv1.fused(), x, cat, 0, lib.ACT_SILU)
                 self._ops.append(dict(kind=lib.OP_SPPF_POOL, name=p + ".m", act=0, H=x.H, W=x.W, Cin=c_, Cout=3 * c_,
-                                      segs=[Seg(cat, c_, 0)], out=cat, out_coff=c_))
+                                      segs=[Seg(cat, c_, 0)], out=cat, out_coff=c_, raw=()))
                 out = self._alloc(x.H, x.W, node.cout)
                 self._conv1x1(p + ".cv2", *m.cv2.fused(), TV([Seg(cat, 4 * c_)], x.H, x.W), out, 0, lib.ACT_SILU)
                 y.append(TV([Seg(out, node.cout)], x.H, x.W))
@@ -382,15 +388,17 @@ class Plan:
                     assert wc.shape == wr.shape
                     u = self._alloc(x.H, x.W, 2 * c)
                     self._ops.append(dict(kind=lib.OP_DWCONV, name=p + ".cls_reg_conv", act=lib.ACT_NONE, H=x.H, W=x.W, Cin=c, Cout=2 * c, ksize=wc.shape[-1],
+                                          raw=(torch.cat([wc, wr], 0).detach().float().cpu(), torch.cat([bc, brg], 0).detach().float().cpu()),
                                           segs=tv.segs, out=u, out_coff=0, w=self._wput(pack.pack_dw(torch.cat([wc, wr], 0), self.dtype)),
                                           b=self._wput(torch.cat([bc, brg], 0).float().cpu()),
                                           aux=[None, self._wput(pack.pack_dw_pairs(torch.cat([wc, wr], 0)))] if self.dtype == lib.F16 and c % 8 == 0 else []))
                     us = [(u, 0), (u, c)]
                     recs = [pack.pack_head_tail(*getattr(m, br + "_conv_s").fused(), pr.weight.detach(), pr.bias.detach())
                             for br, pr in (("cls", m.cls_pred), ("reg", m.reg_pred))]
+                    raw = sum((_raw(*getattr(m, br + "_conv_s").fused(), pr.weight, pr.bias) for br, pr in (("cls", m.cls_pred), ("reg", m.reg_pred))), ())
                     self._ops.append(dict(kind=lib.OP_HEADTAIL, name=p + ".tail", act=0, H=x.H, W=x.W, Cin=c, Cout=5 + self.nc,
                                           segs=[Seg(us[0][0], c, us[0][1]), Seg(us[1][0], c, us[1][1])], out=None, out_coff=0, w=self._wput(recs[0]), b=0,
-                                          aux=[self._wput(recs[1])], level=len(self.head_bufs)))
+                                          aux=[self._wput(recs[1])], level=len(self.head_bufs), raw=raw))
                     self.head_bufs.append((t, None, None))
                     y.append(None)
                     continue
@@ -403,6 +411,7 @@ class Plan:
                     if wc.shape == wr.shape:
                         u2 = self._alloc(x.H, x.W, 2 * c)
                         self._ops.append(dict(kind=lib.OP_DWCONV, name=p + ".cls_reg_conv", act=lib.ACT_NONE, H=x.H, W=x.W, Cin=c, Cout=2 * c, ksize=wc.shape[-1],
+                                              raw=(torch.cat([wc, wr], 0).detach().float().cpu(), torch.cat([bc, brg], 0).detach().float().cpu()),
                                               segs=tv.segs, out=u2, out_coff=0, w=self._wput(pack.pack_dw(torch.cat([wc, wr], 0), self.dtype)),
                                               b=self._wput(torch.cat([bc, brg], 0).float().cpu()),
                                               aux=[None, self._wput(pack.pack_dw_pairs(torch.cat([wc, wr], 0)))]))

@@ -359,18 +359,11 @@ def _stream_lds_ok(ksteps, ct):
     return stream_lds_ok(ksteps, ct)
 
 
-def _conv_choice(x, xs, B, H, W, K, Nc, dt, w2d, rows, cols, transpose, want_stats=False):
-    """(tile_p, tile_c, tile_k) for the single-source conv K -> Nc over x (w2d [rows][cols] as maf_pack_w1x1 takes it).  want_stats: the conv feeds a training-mode
-    BatchNorm — a tile with the statistics epilogue (csrc/conv_stream_lds_st.hip) may cost what the statistics pass it removes would (launch + one read of the
-    output) more than the fastest tile and still be chosen; kept under a key of its own (a data-gradient conv of the same shape has no use for it)."""
-    M = B * H * W
+def conv_candidates(M, K, Nc):
+    """(tile_p, tile_c, tile_k) of every launch `_conv_choice` times for the single-source fp16 1x1 conv K -> Nc over M pixels, in timing order: tile_p x tile_c of
+    the generic kernel, split-K, the persistent "stream" and stream + LDS forms (with the eight-wave one), LDS-shared weight fragments and their DMA ring — and
+    the static rule's tile (pack.tile_for) last if none of them is it."""
     pt0, ct0 = pack.tile_for(Nc, M)
-    if not conv_autotune or dt != lib.F16 or not x.is_cuda:
-        return pt0, ct0, 1
-    key = (M, K, Nc, xs, "st") if want_stats else (M, K, Nc, xs)
-    best = _conv_tune.get(key)
-    if best is not None:
-        return best
     ksteps = -(-K // 32)
     cands = []
     for ct in (2, 4, 6, 8):
@@ -397,6 +390,22 @@ def _conv_choice(x, xs, B, H, W, K, Nc, dt, w2d, rows, cols, transpose, want_sta
                         cands.append((pt, ct, 8))                                # ... by DMA, two k-steps per barrier (csrc/conv_mfma_dma.hip)
     if (pt0, ct0, 1) not in cands:
         cands.append((pt0, ct0, 1))
+    return cands
+
+
+def _conv_choice(x, xs, B, H, W, K, Nc, dt, w2d, rows, cols, transpose, want_stats=False):
+    """(tile_p, tile_c, tile_k) for the single-source conv K -> Nc over x (w2d [rows][cols] as maf_pack_w1x1 takes it).  want_stats: the conv feeds a training-mode
+    BatchNorm — a tile with the statistics epilogue (csrc/conv_stream_lds_st.hip) may cost what the statistics pass it removes would (launch + one read of the
+    output) more than the fastest tile and still be chosen; kept under a key of its own (a data-gradient conv of the same shape has no use for it)."""
+    M = B * H * W
+    pt0, ct0 = pack.tile_for(Nc, M)
+    if not conv_autotune or dt != lib.F16 or not x.is_cuda:
+        return pt0, ct0, 1
+    key = (M, K, Nc, xs, "st") if want_stats else (M, K, Nc, xs)
+    best = _conv_tune.get(key)
+    if best is not None:
+        return best
+    cands = conv_candidates(M, K, Nc)
     out = _empty((B, Nc, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     torch.cuda.synchronize(x.device)                                            # a quiet chip: the side stream's weight gradients would be in the timings
     timer, st, res, packs = lib.Timer(), _stream(x.device), [], {}

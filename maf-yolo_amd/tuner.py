@@ -104,11 +104,216 @@ def p2_wave_bytes(th, tw, k):
 
 
 
+_TUNED_KINDS = (lib.OP_STEM2, lib.OP_HEADTAIL, lib.OP_DWCONV, lib.OP_CONV1X1, lib.OP_CONV3X3S2)
+
+
+class Candidate:
+    """One launch the tuner times for an op.  `tiles`: what `_TUNE_CACHE` stores for it ((rows, 0, workgroups) of a stem pair, (0, 0, iterations) of a head tail,
+    (tile_p, tile_c, tile_k) otherwise); `op`: a copy of the plan's MafOp with the candidate's tile fields, packed weights / bias and twin operands; `keep`: the
+    tensors `op` points into; `pairs`: the op reads its source as pixel pairs (src[0].mode = SRC_PAIRS), so in a plan its producer stores them (out_pairs = 1)."""
+    __slots__ = ("tiles", "op", "keep", "pairs")
+
+    def __init__(self, tiles, op, keep=(), pairs=False):
+        self.tiles, self.op, self.keep, self.pairs = tuple(tiles), op, list(keep), pairs
+
+    def __repr__(self):
+        return "Candidate(%r%s)" % (self.tiles, ", pairs" if self.pairs else "")
+
+
+def _feeds_pairs(plan, i):
+    # a 1x1 conv whose only reader is a depth-wise conv can hand it PIXEL PAIRS — but only from the LDS-resident-weight kernel (tile_k = 5)
+    o = plan.ops[i]
+    if not (o.kind == lib.OP_CONV1X1 and i + 1 < len(plan.ops) and plan.ops[i + 1].kind == lib.OP_DWCONV):
+        return False
+    keep_tk, o.tile_k = o.tile_k, 5
+    try:
+        return plan._pairs_producer(i + 1) is not None
+    finally:
+        o.tile_k = keep_tk
+
+
+def signature(plan, i):
+    """The `_TUNE_CACHE` key of op i of `plan`, or None for an op the tuner does not time."""
+    o, r = plan.ops[i], plan._ops[i]
+    if o.kind == lib.OP_STEM2:
+        return (o.kind, plan.dtype, plan.in_dtype, plan.B, o.H, o.W, o.ksize, o.Cout, o.nc)
+    if o.kind == lib.OP_HEADTAIL:
+        return (o.kind, plan.dtype, plan.B, o.H, o.W, o.Cin, "percu")
+    if o.kind == lib.OP_DWCONV:
+        return (o.kind, plan.dtype, plan.B, o.H, o.W, o.Cin, o.ksize, o.act) + ((o.Cout,) if o.Cout != o.Cin else ())
+    if o.kind not in (lib.OP_CONV1X1, lib.OP_CONV3X3S2):
+        return None
+    M = plan.B * o.H * o.W
+    return (o.kind, plan.dtype, M, o.Cin, o.Cout, o.nsrc, tuple(o.src[k].mode for k in range(o.nsrc)), int(o.out_f32)) + (("twin",) if r.get("twin") else ()) \
+        + (("pool1",) if r.get("pool1") else ()) + (("pairs",) if _feeds_pairs(plan, i) else ())
+
+
+def packed(plan, i, wt, bt, ct, tk):
+    """(weights, bias) of conv op i packed for tile_c = ct, tile_k = tk (device tensors; one record with the bias inside for tile_k 6 / 7)."""
+    o, r = plan.ops[i], plan._ops[i]
+    pool1, srcC = r.get("pool1"), r["raw"][2]
+    wp_ = ((pack.pack_mprep_wreg if tk == 7 else pack.pack_mprep_lds)(wt, bt, *pool1) if pool1 else pack.pack_conv3x3_lds(wt, bt) if tk == 6 else pack.pack_conv3x3_wreg(wt, bt) if tk == 7
+           else pack.pack_conv1x1(wt, srcC, ct, plan.dtype) if o.kind == lib.OP_CONV1X1 else pack.pack_conv3x3(wt, ct, plan.dtype)).to(plan.device)
+    return wp_, pack.pack_bias(bt, ct if tk not in (6, 7) else 4).to(plan.device)
+
+
+def conv_tiles(plan, i):
+    """(tile_p, tile_c, tile_k) of every variant the tuner times for conv op i (OP_CONV1X1 / OP_CONV3X3S2), in timing order."""
+    o, r = plan.ops[i], plan._ops[i]
+    M = plan.B * o.H * o.W
+    twin, pool1 = r.get("twin"), r.get("pool1")
+    cands = []
+    for ct in (2, 4, 6, 8):
+        nt = -(-o.Cout // (16 * ct))
+        if nt * 16 * ct > 2 * max(o.Cout, 32) or (ct == 8 and o.out_stride % 8 and not o.out_f32 and plan.dtype == lib.F16):
+            continue
+        for pt in (1, 2, 4):
+            if pt == 4 and ct > 4:
+                continue
+            if -(-M // (64 * pt)) * nt < 256 and pt > 1:
+                continue                          # would not fill the chip
+            cands.append((pt, ct, 1))
+        ksteps = sum(-(-o.src[k].C // (32 if plan.dtype == lib.F16 else 16)) for k in range(o.nsrc)) * (9 if o.kind == lib.OP_CONV3X3S2 else 1)
+        if ksteps >= 8 and M <= 65536:
+            cands.append((1, ct, 4))                 # split-K across the 4 waves: long reductions on small maps
+        direct = o.kind == lib.OP_CONV1X1 and o.nsrc == 1 and o.src[0].mode == lib.SRC_DIRECT
+        if direct and plan.dtype == lib.F16 and not o.out_f32 and ksteps <= 4 and ksteps * ct <= 16:
+            for pt in (1, 2):                                # persistent waves, next tile's activations in flight during the epilogue
+                cands.append((pt, ct, 3))
+        if o.kind == lib.OP_CONV1X1 and plan.dtype == lib.F16 and not o.out_f32 and stream_lds_ok(ksteps, ct) \
+                and (o.nsrc == 1 or all(o.src[k].mode != lib.SRC_POOL2 for k in range(o.nsrc))) and (direct or ct >= 4 or o.nsrc == 1):
+            cands.append((1, ct, 5))                         # persistent waves, the channel tile's weights resident in LDS
+            if ct >= 4 and 64 <= ksteps * ct <= 160 and (8 <= ksteps <= 20 or ksteps == 24):
+                cands.append((2, ct, 5))                     # ... eight waves behind one copy of the weights where the LDS leaves room for one or two workgroups per CU (conv_stream_lds_w8.hip)
+        if o.kind == lib.OP_CONV3X3S2 and plan.dtype == lib.F16 and (o.Cin, o.Cout) in ((48, 48), (48, 64), (64, 64)) and ct == 4 and (M >= 65536 or pool1):
+            for wg in (4, 8, 12, 16):                         # weights + input patch in LDS, 256 .. 1024 persistent workgroups (tile_c = workgroups / 64)
+                cands.append((4, wg, 6))
+        if o.kind == lib.OP_CONV3X3S2 and plan.dtype == lib.F16 and pack.conv3x3_wreg_shape(o.Cin, o.Cout) and ct == 4:
+            for wg in (2, 4, 8):                              # weights in registers, patches by DMA: 64 / 128 / 256 workgroups per conv (tile_c = that / 32)
+                if wg * 32 * (2 if twin else 1) <= 256:
+                    cands += [(3, wg, 7), (2, wg, 7)]         # tile_p = patch buffers (3: two patches in flight ahead of the multiply)
+        pooled = o.nsrc == 1 and o.src[0].mode == lib.SRC_POOL2
+        if ksteps >= 4 and ct >= 4 and plan.dtype == lib.F16 and not o.out_f32 and not pooled:
+            for pt in ((1, 2, 4) if ct == 4 else (1, 2)):     # the workgroup shares each k-step's weight fragments through LDS
+                if pt == 1 or -(-M // (64 * pt)) * nt >= 256:
+                    cands.append((pt, ct, 2))
+                    if pt <= 2 and ksteps >= 8:                # ... that arrive by DMA, two k-steps per barrier, three stages ahead (K-heavy layers)
+                        cands.append((pt, ct, 8))
+    if twin:
+        cands = [c_ for c_ in cands if c_[2] in (1, 2, 4, 7, 8)] # the variants that take a twin launch
+    if pool1:
+        cands = [c_ for c_ in cands if c_[2] == r.get("pool1_tk", 6)]   # only the workgroup count (and the patch buffers of tile_k = 7) are open
+    return cands
+
+
+def dw_tiles(plan, i):
+    """(tile_p, tile_c, tile_k) of every variant the tuner times for depth-wise op i, in timing order: the v_fma_mix kernel's (rows, columns, channel block), then
+    dot2 (tile_p = -2), pixel pairs (tile_p = -4; only where the 1x1 conv in front, as the plan stands, can store pairs) and the matrix-core form (tile_p = -1)."""
+    o = plan.ops[i]
+    n = 8 if plan.dtype == lib.F16 else 4
+    out = []
+    # tile heights / widths: powers of two plus the map's own size and its half (40 x 40 and 20 x 20 maps: tiles that
+    # divide the map exactly have no half-empty edge tiles and the smallest halo share)
+    ths = sorted({4, 8, 16, 32} | {v for v in (o.H, o.H // 2) if 8 <= v <= 40})
+    tws = sorted({8, 16, 32} | {v for v in (o.W, o.W // 2) if 8 <= v <= 40 and v % 4 == 0})
+    for th in ths:
+        for tw in tws:
+            for cbm in (8, 4, 2):
+                t_h, t_w, cb = min(th, o.H), min(tw, -(-o.W // 4) * 4), min(cbm * n, -(-o.Cin // n) * n)
+                lds = ((t_h + o.ksize - 1) * (t_w + o.ksize - 1) * (cb // n + 2) + o.ksize * o.ksize * (cb // n)) * 16
+                if lds > 96 * 1024 or (t_h, t_w, cb) in out:
+                    continue
+                out.append((t_h, t_w, cb))
+    if plan.dtype == lib.F16:                            # two taps per instruction (csrc/dwconv_dot2.hip): tile_p = -2, tile_c = columns, tile_k = rows * 256 + channels
+        w8 = -(-o.W // 8) * 8
+        for th in sorted({4, 8, 10, 16, 20} | ({o.H} if o.H <= 40 else set())):
+            if th > o.H:
+                continue
+            for tw in sorted({16, 24, 32, 40} | ({w8} if w8 <= 40 else set())):
+                if tw > w8:
+                    continue
+                for cb in (16, 32, 64):
+                    cb = min(cb, o.Cin)
+                    nq, np_ = cb // 4, (o.ksize + 1) // 2
+                    lds = ((th + o.ksize - 1) * ((tw + o.ksize - 1) // 2) * (nq + 3) + o.ksize * 2 * np_ * nq) * 16      # (pair stride <= nq + 3: csrc/dwconv_dot2.hip)
+                    if lds > 96 * 1024 or (-2, tw, th * 256 + cb) in out:
+                        continue
+                    out.append((-2, tw, th * 256 + cb))
+    if plan._pairs_producer(i) is not None:              # pixel-pair input, v_dot2c with scalar weight pairs (csrc/dwconv_p2.hip): tile_p = -4, tile_c = columns, tile_k = rows * 256 + waves per workgroup
+        w4 = -(-o.W // 4) * 4
+        for th in sorted({4, 5, 8, 10, 16, 20} | ({o.H} if o.H <= 40 else set())):
+            if th > o.H:
+                continue
+            for tw in sorted({16, 20, 32, 40, 80} | ({w4} if w4 <= 80 else set())):
+                if tw > w4:
+                    continue
+                plane = p2_wave_bytes(th, tw, o.ksize)
+                if plane > 20 * 1024:                    # fewer than 8 waves per CU: never the fastest
+                    continue
+                for nw, stg in ((2, 0), (4, 0), (8, 0), (2, 128), (4, 128), (8, 128)):
+                    # + 128: staged stores (the waves of a workgroup = adjacent channel groups of one tile, results through the dead planes,
+                    # nw x 16-byte runs per pixel): where the kernel takes that form (csrc/dwconv_p2.hip:maf_launch_dwconv_p2)
+                    if stg and not ((o.Cin // 8) % nw == 0 and th * (tw // 4) <= 64 and plane >= 4160 and o.Cout <= 2 * o.Cin and _P2_STAGE):
+                        continue
+                    out.append((-4, tw, th * 256 + nw + stg))
+    if plan.dtype == lib.F16 and o.aux[0]:               # matrix-core variant (csrc/dwconv_mfma.hip): tile_p = -1
+        out.append((-1, 0, 0))
+    return out
+
+
+def candidates(plan, i):
+    """Every launch the tuner times for op i of `plan`, in timing order (a list of `Candidate`; empty for an op it does not time).  Stem pairs: tile height (8 / 4
+    rows; 4 only for the 48 -> 96 stem, whose kernel takes no other) x persistent workgroups; head tails: persistent iterations per CU; depth-wise: `dw_tiles`;
+    1x1 and 3x3 stride-2 convs: `conv_tiles`, each with its own weight packing.  The list of a depth-wise op depends on the tile_k its producer holds (pixel pairs
+    only behind tile_k = 5), so it is what the tuner offers at the point it reaches op i.  The stem's image (src[0].ptr) and the head tail's output are the plan
+    op's: the caller points them at real buffers."""
+    o, r = plan.ops[i], plan._ops[i]
+    if o.kind == lib.OP_STEM2:
+        out = []
+        for rows in ((4,) if o.Cout == 96 else (8, 4)):
+            for wgs in (256, 512, 768, 1024):
+                op = lib.MafOp.from_buffer_copy(o)
+                op.tile_p, op.tile_k = rows, wgs
+                out.append(Candidate((rows, 0, wgs), op))
+        return out
+    if o.kind == lib.OP_HEADTAIL:
+        out = []
+        for iters in (1, 2, 3, 4, 6):
+            op = lib.MafOp.from_buffer_copy(o)
+            op.tile_k = iters
+            out.append(Candidate((0, 0, iters), op))
+        return out
+    if o.kind == lib.OP_DWCONV:
+        out = []
+        for tp, tc, tk in dw_tiles(plan, i):
+            op = lib.MafOp.from_buffer_copy(o)
+            op.tile_p, op.tile_c, op.tile_k = tp, tc, tk
+            op.src[0].mode = lib.SRC_PAIRS if tp == -4 else lib.SRC_DIRECT
+            out.append(Candidate((tp, tc, tk), op, pairs=tp == -4))
+        return out
+    if o.kind not in (lib.OP_CONV1X1, lib.OP_CONV3X3S2):
+        return []
+    w, b = r["raw"][:2]
+    twin = r.get("twin")
+    packs, out = {}, []
+    for pt, ct, tk in conv_tiles(plan, i):
+        form = (ct if tk not in (6, 7) else 0, tk if tk in (6, 7) else 0)
+        if form not in packs:
+            packs[form] = packed(plan, i, w, b, ct, tk) + (packed(plan, i, *twin["raw"], ct, tk) if twin else ())
+        keep = packs[form]
+        op = lib.MafOp.from_buffer_copy(o)
+        op.tile_p, op.tile_c, op.tile_k, op.w, op.bias = pt, ct, tk, keep[0].data_ptr(), keep[1].data_ptr()
+        op.out_pairs = 0
+        if twin:
+            op.aux[1], op.aux[2] = keep[2].data_ptr(), keep[3].data_ptr()
+        out.append(Candidate((pt, ct, tk), op, keep))
+    return out
+
+
 def autotune(plan, x, reps=5, verbose=False):
-    """Time every (tile_p, tile_c) candidate of every MFMA conv on this device and keep the fastest.
-    The candidates differ only in how the (pixel x channel) space is cut into wave tiles (and in the matching weight
-    packing); results are cached per layer signature in `_TUNE_CACHE` so other plans of the same model reuse them."""
-    import time
+    """Time every candidate (`candidates`) of every stem pair, head tail, depth-wise and MFMA conv launch on this device and keep the fastest.
+    The candidates differ only in how the work is cut into wave tiles / workgroups (and in the matching weight packing); results are cached per
+    layer signature in `_TUNE_CACHE` so other plans of the same model reuse them."""
     assert x.is_cuda
     L = lib.load()
     stream = torch.cuda.current_stream(plan.device)
@@ -118,26 +323,29 @@ def autotune(plan, x, reps=5, verbose=False):
     timer = lib.Timer()
     plan._tuned = getattr(plan, "_tuned", [])
     changed = 0
+
+    def timed(cands):
+        res = []
+        for c_ in cands:
+            lib.check(L.maf_op_launch(C.byref(c_.op), stream.cuda_stream))          # warm-up
+            ts = []
+            for _ in range(reps):
+                timer.start(stream.cuda_stream)
+                lib.check(L.maf_op_launch(C.byref(c_.op), stream.cuda_stream))
+                timer.stop(stream.cuda_stream)
+                ts.append(timer.elapsed_ms())
+            res.append((min(ts),) + c_.tiles)
+        return res
+
     for i, (o, r) in enumerate(zip(plan.ops, plan._ops)):
+        sig = signature(plan, i)
+        if sig is None:
+            continue
+        best = _TUNE_CACHE.get(sig)
         if o.kind == lib.OP_STEM2:                           # stem pair: tile height (8 / 4 rows) and number of persistent workgroups
-            sig = (o.kind, plan.dtype, plan.in_dtype, plan.B, o.H, o.W, o.ksize, o.Cout, o.nc)
-            best = _TUNE_CACHE.get(sig)
             if best is None:
                 o.src[0].ptr = x.data_ptr()
-                results = []
-                for rows in (8, 4):
-                    for wgs in (256, 512, 768, 1024):
-                        op = lib.MafOp.from_buffer_copy(o)
-                        op.tile_p, op.tile_k = rows, wgs
-                        lib.check(L.maf_op_launch(C.byref(op), stream.cuda_stream))
-                        ts = []
-                        for _ in range(reps):
-                            timer.start(stream.cuda_stream)
-                            lib.check(L.maf_op_launch(C.byref(op), stream.cuda_stream))
-                            timer.stop(stream.cuda_stream)
-                            ts.append(timer.elapsed_ms())
-                        results.append((min(ts), rows, wgs))
-                results.sort()
+                results = sorted((t, rows, wgs) for t, rows, _, wgs in timed(candidates(plan, i)))
                 best = (results[0][1], 0, results[0][2])
                 _TUNE_CACHE[sig] = best
                 if verbose:
@@ -147,23 +355,9 @@ def autotune(plan, x, reps=5, verbose=False):
                 changed += 1
             continue
         if o.kind == lib.OP_HEADTAIL:                        # head tail: persistent workgroups per CU (tile_k; the weights are staged once per workgroup)
-            sig = (o.kind, plan.dtype, plan.B, o.H, o.W, o.Cin, "percu")
-            best = _TUNE_CACHE.get(sig)
             if best is None:
                 o.out = pred.data_ptr()
-                results = []
-                for iters in (1, 2, 3, 4, 6):
-                    op = lib.MafOp.from_buffer_copy(o)
-                    op.tile_k = iters
-                    lib.check(L.maf_op_launch(C.byref(op), stream.cuda_stream))
-                    ts = []
-                    for _ in range(reps):
-                        timer.start(stream.cuda_stream)
-                        lib.check(L.maf_op_launch(C.byref(op), stream.cuda_stream))
-                        timer.stop(stream.cuda_stream)
-                        ts.append(timer.elapsed_ms())
-                    results.append((min(ts), iters))
-                results.sort()
+                results = sorted((t, it) for t, _, _, it in timed(candidates(plan, i)))
                 best = (0, 0, results[0][1])
                 _TUNE_CACHE[sig] = best
                 if verbose:
@@ -173,95 +367,8 @@ def autotune(plan, x, reps=5, verbose=False):
                 changed += 1
             continue
         if o.kind == lib.OP_DWCONV:                          # depth-wise: workgroup tile (rows, cols, channel block)
-            sig = (o.kind, plan.dtype, plan.B, o.H, o.W, o.Cin, o.ksize, o.act) + ((o.Cout,) if o.Cout != o.Cin else ())
-            best = _TUNE_CACHE.get(sig)
             if best is None:
-                n = 8 if plan.dtype == lib.F16 else 4
-                results = []
-                # tile heights / widths: powers of two plus the map's own size and its half (40 x 40 and 20 x 20 maps: tiles that
-                # divide the map exactly have no half-empty edge tiles and the smallest halo share)
-                ths = sorted({4, 8, 16, 32} | {v for v in (o.H, o.H // 2) if 8 <= v <= 40})
-                tws = sorted({8, 16, 32} | {v for v in (o.W, o.W // 2) if 8 <= v <= 40 and v % 4 == 0})
-                for th in ths:
-                    for tw in tws:
-                        for cbm in (8, 4, 2):
-                            t_h, t_w, cb = min(th, o.H), min(tw, -(-o.W // 4) * 4), min(cbm * n, -(-o.Cin // n) * n)
-                            lds = ((t_h + o.ksize - 1) * (t_w + o.ksize - 1) * (cb // n + 2) + o.ksize * o.ksize * (cb // n)) * 16
-                            if lds > 96 * 1024 or (t_h, t_w, cb) in [(a, b2, c2) for _, a, b2, c2 in results]:
-                                continue
-                            op = lib.MafOp.from_buffer_copy(o)
-                            op.tile_p, op.tile_c, op.tile_k = t_h, t_w, cb
-                            lib.check(L.maf_op_launch(C.byref(op), stream.cuda_stream))
-                            ts = []
-                            for _ in range(reps):
-                                timer.start(stream.cuda_stream)
-                                lib.check(L.maf_op_launch(C.byref(op), stream.cuda_stream))
-                                timer.stop(stream.cuda_stream)
-                                ts.append(timer.elapsed_ms())
-                            results.append((min(ts), t_h, t_w, cb))
-                if plan.dtype == lib.F16:                            # two taps per instruction (csrc/dwconv_dot2.hip): tile_p = -2, tile_c = columns, tile_k = rows * 256 + channels
-                    w8 = -(-o.W // 8) * 8
-                    for th in sorted({4, 8, 10, 16, 20} | ({o.H} if o.H <= 40 else set())):
-                        if th > o.H:
-                            continue
-                        for tw in sorted({16, 24, 32, 40} | ({w8} if w8 <= 40 else set())):
-                            if tw > w8:
-                                continue
-                            for cb in (16, 32, 64):
-                                cb = min(cb, o.Cin)
-                                nq, np_ = cb // 4, (o.ksize + 1) // 2
-                                lds = ((th + o.ksize - 1) * ((tw + o.ksize - 1) // 2) * (nq + 3) + o.ksize * 2 * np_ * nq) * 16      # (pair stride <= nq + 3: csrc/dwconv_dot2.hip)
-                                if lds > 96 * 1024 or (-2, tw, th * 256 + cb) in [r_[1:] for r_ in results]:
-                                    continue
-                                op = lib.MafOp.from_buffer_copy(o)
-                                op.tile_p, op.tile_c, op.tile_k = -2, tw, th * 256 + cb
-                                lib.check(L.maf_op_launch(C.byref(op), stream.cuda_stream))
-                                ts = []
-                                for _ in range(reps):
-                                    timer.start(stream.cuda_stream)
-                                    lib.check(L.maf_op_launch(C.byref(op), stream.cuda_stream))
-                                    timer.stop(stream.cuda_stream)
-                                    ts.append(timer.elapsed_ms())
-                                results.append((min(ts), -2, tw, th * 256 + cb))
-                if plan._pairs_producer(i) is not None:              # pixel-pair input, v_dot2c with scalar weight pairs (csrc/dwconv_p2.hip): tile_p = -4, tile_c = columns, tile_k = rows * 256 + waves per workgroup
-                    w4 = -(-o.W // 4) * 4
-                    for th in sorted({4, 5, 8, 10, 16, 20} | ({o.H} if o.H <= 40 else set())):
-                        if th > o.H:
-                            continue
-                        for tw in sorted({16, 20, 32, 40, 80} | ({w4} if w4 <= 80 else set())):
-                            if tw > w4:
-                                continue
-                            plane = p2_wave_bytes(th, tw, o.ksize)
-                            if plane > 20 * 1024:                    # fewer than 8 waves per CU: never the fastest
-                                continue
-                            for nw, stg in ((2, 0), (4, 0), (8, 0), (2, 128), (4, 128), (8, 128)):
-                                # + 128: staged stores (the waves of a workgroup = adjacent channel groups of one tile, results through the dead planes,
-                                # nw x 16-byte runs per pixel): where the kernel takes that form (csrc/dwconv_p2.hip:maf_launch_dwconv_p2)
-                                if stg and not ((o.Cin // 8) % nw == 0 and th * (tw // 4) <= 64 and plane >= 4160 and o.Cout <= 2 * o.Cin and _P2_STAGE):
-                                    continue
-                                op = lib.MafOp.from_buffer_copy(o)
-                                op.tile_p, op.tile_c, op.tile_k = -4, tw, th * 256 + nw + stg
-                                op.src[0].mode = lib.SRC_PAIRS       # (the NHWC content of the buffer read as pairs: same work)
-                                lib.check(L.maf_op_launch(C.byref(op), stream.cuda_stream))
-                                ts = []
-                                for _ in range(reps):
-                                    timer.start(stream.cuda_stream)
-                                    lib.check(L.maf_op_launch(C.byref(op), stream.cuda_stream))
-                                    timer.stop(stream.cuda_stream)
-                                    ts.append(timer.elapsed_ms())
-                                results.append((min(ts), -4, tw, th * 256 + nw + stg))
-                if plan.dtype == lib.F16 and o.aux[0]:               # matrix-core variant (csrc/dwconv_mfma.hip): tile_p = -1
-                    op = lib.MafOp.from_buffer_copy(o)
-                    op.tile_p, op.tile_c, op.tile_k = -1, 0, 0
-                    lib.check(L.maf_op_launch(C.byref(op), stream.cuda_stream))
-                    ts = []
-                    for _ in range(reps):
-                        timer.start(stream.cuda_stream)
-                        lib.check(L.maf_op_launch(C.byref(op), stream.cuda_stream))
-                        timer.stop(stream.cuda_stream)
-                        ts.append(timer.elapsed_ms())
-                    results.append((min(ts), -1, 0, 0))
-                results.sort()
+                results = sorted(timed(candidates(plan, i)))     # (pixel-pair candidates read the NHWC content of the buffer as pairs: same work)
                 best = results[0][1:]
                 _TUNE_CACHE[sig] = best
                 _TUNE_CACHE[sig + ("nhwc",)] = [r_ for r_ in results if r_[1] != -4][0][1:]      # for a plan whose producer cannot store pixel pairs
@@ -282,93 +389,20 @@ def autotune(plan, x, reps=5, verbose=False):
                     prod.out_pairs = pairs                           # the 1x1 conv in front stores what this kernel reads
                 changed += 1
             continue
-        if o.kind not in (lib.OP_CONV1X1, lib.OP_CONV3X3S2):
-            continue
-        M = plan.B * o.H * o.W
-        twin = r.get("twin")
-        pool1 = r.get("pool1")
-        # a 1x1 conv whose only reader is a depth-wise conv can hand it PIXEL PAIRS — but only from the LDS-resident-weight kernel (tile_k = 5).  Timed alone, the
-        # register-weight form sometimes wins such a layer by a few hundred nanoseconds (run-to-run noise) and the depth-wise conv behind it then loses its pair
-        # input (n, 20 x 20 x 288, k = 9: 20.9 -> 27.9 us): where pairs are possible, tile_k = 5 is kept unless another variant is clearly (1.3x) faster.
-        feeds_pairs = False
-        if o.kind == lib.OP_CONV1X1 and i + 1 < len(plan.ops) and plan.ops[i + 1].kind == lib.OP_DWCONV:
-            keep_tk, o.tile_k = o.tile_k, 5
-            feeds_pairs = plan._pairs_producer(i + 1) is not None
-            o.tile_k = keep_tk
-        sig = (o.kind, plan.dtype, M, o.Cin, o.Cout, o.nsrc, tuple(o.src[k].mode for k in range(o.nsrc)), int(o.out_f32)) + (("twin",) if twin else ()) + (("pool1",) if pool1 else ()) \
-            + (("pairs",) if feeds_pairs else ())
-        best = _TUNE_CACHE.get(sig)
-        w, b, srcC = r["raw"]
-
-        def packed(wt, bt, ct_, tk_):
-            wp_ = ((pack.pack_mprep_wreg if tk_ == 7 else pack.pack_mprep_lds)(wt, bt, *pool1) if pool1 else pack.pack_conv3x3_lds(wt, bt) if tk_ == 6 else pack.pack_conv3x3_wreg(wt, bt) if tk_ == 7 else pack.pack_conv1x1(wt, srcC, ct_, plan.dtype) if o.kind == lib.OP_CONV1X1 else pack.pack_conv3x3(wt, ct_, plan.dtype)).to(plan.device)
-            return wp_, pack.pack_bias(bt, ct_ if tk_ not in (6, 7) else 4).to(plan.device)
+        twin, pool1 = r.get("twin"), r.get("pool1")
         if best is None:
-            cands = []
-            for ct in (2, 4, 6, 8):
-                nt = -(-o.Cout // (16 * ct))
-                if nt * 16 * ct > 2 * max(o.Cout, 32) or (ct == 8 and o.out_stride % 8 and not o.out_f32 and plan.dtype == lib.F16):
-                    continue
-                for pt in (1, 2, 4):
-                    if pt == 4 and ct > 4:
-                        continue
-                    if -(-M // (64 * pt)) * nt < 256 and pt > 1:
-                        continue                          # would not fill the chip
-                    cands.append((pt, ct, 1))
-                ksteps = sum(-(-o.src[k].C // (32 if plan.dtype == lib.F16 else 16)) for k in range(o.nsrc)) * (9 if o.kind == lib.OP_CONV3X3S2 else 1)
-                if ksteps >= 8 and M <= 65536:
-                    cands.append((1, ct, 4))                 # split-K across the 4 waves: long reductions on small maps
-                direct = o.kind == lib.OP_CONV1X1 and o.nsrc == 1 and o.src[0].mode == lib.SRC_DIRECT
-                if direct and plan.dtype == lib.F16 and not o.out_f32 and ksteps <= 4 and ksteps * ct <= 16:
-                    for pt in (1, 2):                                # persistent waves, next tile's activations in flight during the epilogue
-                        cands.append((pt, ct, 3))
-                if o.kind == lib.OP_CONV1X1 and plan.dtype == lib.F16 and not o.out_f32 and stream_lds_ok(ksteps, ct) \
-                        and (o.nsrc == 1 or all(o.src[k].mode != lib.SRC_POOL2 for k in range(o.nsrc))) and (direct or ct >= 4 or o.nsrc == 1):
-                    cands.append((1, ct, 5))                         # persistent waves, the channel tile's weights resident in LDS
-                    if ct >= 4 and 64 <= ksteps * ct <= 160 and (8 <= ksteps <= 20 or ksteps == 24):
-                        cands.append((2, ct, 5))                     # ... eight waves behind one copy of the weights where the LDS leaves room for one or two workgroups per CU (conv_stream_lds_w8.hip)
-                if o.kind == lib.OP_CONV3X3S2 and plan.dtype == lib.F16 and (o.Cin, o.Cout) in ((48, 48), (48, 64), (64, 64)) and ct == 4 and (M >= 65536 or pool1):
-                    for wg in (4, 8, 12, 16):                         # weights + input patch in LDS, 256 .. 1024 persistent workgroups (tile_c = workgroups / 64)
-                        cands.append((4, wg, 6))
-                if o.kind == lib.OP_CONV3X3S2 and plan.dtype == lib.F16 and pack.conv3x3_wreg_shape(o.Cin, o.Cout) and ct == 4:
-                    for wg in (2, 4, 8):                              # weights in registers, patches by DMA: 64 / 128 / 256 workgroups per conv (tile_c = that / 32)
-                        if wg * 32 * (2 if twin else 1) <= 256:
-                            cands += [(3, wg, 7), (2, wg, 7)]         # tile_p = patch buffers (3: two patches in flight ahead of the multiply)
-                pooled = o.nsrc == 1 and o.src[0].mode == lib.SRC_POOL2
-                if ksteps >= 4 and ct >= 4 and plan.dtype == lib.F16 and not o.out_f32 and not pooled:
-                    for pt in ((1, 2, 4) if ct == 4 else (1, 2)):     # the workgroup shares each k-step's weight fragments through LDS
-                        if pt == 1 or -(-M // (64 * pt)) * nt >= 256:
-                            cands.append((pt, ct, 2))
-                            if pt <= 2 and ksteps >= 8:                # ... that arrive by DMA, two k-steps per barrier, three stages ahead (K-heavy layers)
-                                cands.append((pt, ct, 8))
-            results = []
-            if twin:
-                cands = [c_ for c_ in cands if c_[2] in (1, 2, 4, 7, 8)] # the variants that take a twin launch
-            if pool1:
-                cands = [c_ for c_ in cands if c_[2] == r.get("pool1_tk", 6)]   # only the workgroup count (and the patch buffers of tile_k = 7) are open
-            for pt, ct, tk in cands:
-                wp, bp = packed(w, b, ct, tk)
-                op = lib.MafOp.from_buffer_copy(o)
-                op.tile_p, op.tile_c, op.tile_k, op.w, op.bias = pt, ct, tk, wp.data_ptr(), bp.data_ptr()
-                if twin:
-                    wp2, bp2 = packed(*twin["raw"], ct, tk)
-                    op.aux[1], op.aux[2] = wp2.data_ptr(), bp2.data_ptr()
-                lib.check(L.maf_op_launch(C.byref(op), stream.cuda_stream))          # warm-up
-                ts = []
-                for _ in range(reps):
-                    timer.start(stream.cuda_stream)
-                    lib.check(L.maf_op_launch(C.byref(op), stream.cuda_stream))
-                    timer.stop(stream.cuda_stream)
-                    ts.append(timer.elapsed_ms())
-                results.append((min(ts), pt, ct, tk))
-            results.sort()
+            results = sorted(timed(candidates(plan, i)))
             best = (results[0][1], results[0][2], results[0][3])
-            if feeds_pairs:
+            # where pairs are possible (signature: "pairs"), tile_k = 5 is kept unless another variant is clearly (1.3x) faster.  Timed alone, the register-weight form
+            # sometimes wins such a layer by a few hundred nanoseconds (run-to-run noise) and the depth-wise conv behind it then loses its pair input
+            # (n, 20 x 20 x 288, k = 9: 20.9 -> 27.9 us)
+            if sig[-1] == "pairs":
                 five = [r_ for r_ in results if r_[3] == 5]
                 if five and five[0][0] <= 1.3 * results[0][0]:
                     best = (five[0][1], five[0][2], five[0][3])
             _TUNE_CACHE[sig] = best
             if verbose:
+                M = plan.B * o.H * o.W
                 print("tune %-32s M=%-7d %4d->%-4d: %s" % (plan.op_names[i], M, o.Cin, o.Cout, " ".join("(%d,%d%s)%.1fus" % (p, c, {4: ",k4", 2: ",lds", 3: ",stream", 5: ",streamlds", 6: ",ldsall", 7: ",wreg", 8: ",dma"}.get(k, ""), t * 1e3) for t, p, c, k in results)))
         pt, ct, tk = best
         if pool1:
@@ -377,11 +411,11 @@ def autotune(plan, x, reps=5, verbose=False):
                 changed += 1
             continue
         if (pt, ct, tk) != (o.tile_p, o.tile_c, max(1, o.tile_k)):
-            wp, bp = packed(w, b, ct, tk)
+            wp, bp = packed(plan, i, *r["raw"][:2], ct, tk)
             plan._tuned += [wp, bp]
             o.tile_p, o.tile_c, o.tile_k, o.w, o.bias = pt, ct, tk, wp.data_ptr(), bp.data_ptr()
             if twin:
-                wp2, bp2 = packed(*twin["raw"], ct, tk)
+                wp2, bp2 = packed(plan, i, *twin["raw"], ct, tk)
                 plan._tuned += [wp2, bp2]
                 o.aux[1], o.aux[2] = wp2.data_ptr(), bp2.data_ptr()
             changed += 1

@@ -1004,13 +1004,28 @@ def test_bn_act_with_residual_matches_torch(dtype, act):
     assert torch.allclose(bn.running_var, ref.running_var, rtol=1e-3, atol=1e-4)
 
 
+# the (pixels, K, N) shapes one training step of n at bench.py's batch (32 x 640^2) hands train_ops._conv_choice, forward and data gradient
+_TRAIN_STEP_N32 = [
+    ((32, 20, 20), 72, 192), ((32, 20, 20), 80, 192), ((32, 20, 20), 96, 288), ((32, 20, 20), 192, 68), ((32, 20, 20), 192, 80), ((32, 20, 20), 192, 192), ((32, 20, 20), 192, 288), ((32, 20, 20), 192, 384),
+    ((32, 20, 20), 192, 448), ((32, 20, 20), 192, 480), ((32, 20, 20), 192, 576), ((32, 20, 20), 288, 96), ((32, 20, 20), 288, 192), ((32, 20, 20), 384, 192), ((32, 20, 20), 384, 384), ((32, 20, 20), 384, 576),
+    ((32, 20, 20), 384, 768), ((32, 20, 20), 448, 192), ((32, 20, 20), 480, 192), ((32, 20, 20), 576, 192), ((32, 20, 20), 576, 384), ((32, 20, 20), 768, 384), ((32, 40, 40), 64, 192), ((32, 40, 40), 72, 128),
+    ((32, 40, 40), 80, 128), ((32, 40, 40), 96, 96), ((32, 40, 40), 96, 288), ((32, 40, 40), 128, 68), ((32, 40, 40), 128, 80), ((32, 40, 40), 128, 128), ((32, 40, 40), 128, 192), ((32, 40, 40), 128, 448),
+    ((32, 40, 40), 128, 576), ((32, 40, 40), 192, 64), ((32, 40, 40), 192, 128), ((32, 40, 40), 192, 192), ((32, 40, 40), 192, 288), ((32, 40, 40), 288, 96), ((32, 40, 40), 288, 192), ((32, 40, 40), 448, 128),
+    ((32, 40, 40), 576, 128), ((32, 80, 80), 48, 48), ((32, 80, 80), 48, 144), ((32, 80, 80), 64, 192), ((32, 80, 80), 72, 128), ((32, 80, 80), 80, 128), ((32, 80, 80), 96, 96), ((32, 80, 80), 96, 144),
+    ((32, 80, 80), 128, 68), ((32, 80, 80), 128, 80), ((32, 80, 80), 128, 128), ((32, 80, 80), 128, 192), ((32, 80, 80), 128, 256), ((32, 80, 80), 128, 288), ((32, 80, 80), 144, 48), ((32, 80, 80), 144, 96),
+    ((32, 80, 80), 192, 64), ((32, 80, 80), 192, 128), ((32, 80, 80), 256, 128), ((32, 80, 80), 288, 128), ((32, 160, 160), 24, 72), ((32, 160, 160), 48, 48), ((32, 160, 160), 48, 72), ((32, 160, 160), 72, 24),
+    ((32, 160, 160), 72, 48),
+]
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("M_hw,cin,cout", [((8, 40, 40), 64, 192), ((4, 80, 80), 192, 64), ((8, 20, 20), 288, 96), ((2, 160, 160), 24, 72),
                                            ((2, 4, 4), 576, 384), ((2, 4, 4), 768, 384), ((2, 8, 8), 448, 128), ((2, 4, 4), 96, 288), ((2, 16, 16), 288, 128),
-                                           ((2, 4, 4), 480, 192), ((1, 3, 5), 640, 256), ((2, 16, 16), 48, 48), ((2, 8, 8), 128, 80), ((2, 4, 4), 192, 68)])
+                                           ((2, 4, 4), 480, 192), ((1, 3, 5), 640, 256), ((2, 16, 16), 48, 48), ((2, 8, 8), 128, 80), ((2, 4, 4), 192, 68)] + _TRAIN_STEP_N32)
 def test_every_conv_variant_the_train_tuner_may_pick(M_hw, cin, cout):
-    """train_ops._conv_choice times tile_p x tile_c x {generic, LDS-shared fragments, split-K, stream, stream + LDS} candidates and keeps the
-    fastest: every candidate it can come up with for a shape must compute the same 1x1 conv (fp16 operands, fp32 accumulation)."""
+    """train_ops._conv_choice times the candidates of train_ops.conv_candidates — tile_p x tile_c x {generic, LDS-shared fragments and their DMA ring,
+    split-K, stream, stream + LDS and its eight-wave form} plus the static tile — and keeps the fastest: every one of them must compute the same 1x1 conv
+    (fp16 operands, fp32 accumulation)."""
     import importlib
     train_ops = importlib.import_module("maf-yolo_amd.train_ops")
     lib = importlib.import_module("maf-yolo_amd.lib")
@@ -1020,20 +1035,17 @@ def test_every_conv_variant_the_train_tuner_may_pick(M_hw, cin, cout):
     w = (torch.randn(cout, cin, device="cuda") / cin ** 0.5)
     ref = torch.nn.functional.conv2d(x.float(), w.half().float().reshape(cout, cin, 1, 1))
     M, ksteps = B * H * W, -(-cin // 32)
-    cands = set()
-    for ct in (2, 4, 6, 8):
-        nt = -(-cout // (16 * ct))
-        if nt * 16 * ct > 2 * max(cout, 32) or (ct == 8 and cout % 8):
-            continue
-        cands |= {(pt, ct, 1) for pt in (1, 2, 4) if not (pt == 4 and ct > 4)}
-        cands |= {(1, ct, 4)} if ksteps >= 8 and M <= 65536 else set()
-        cands |= {(1, ct, 3), (2, ct, 3)} if ksteps <= 4 and ksteps * ct <= 16 else set()
-        cands |= {(1, ct, 5)} if train_ops._stream_lds_ok(ksteps, ct) else set()
-        cands |= {(pt, ct, 2) for pt in ((1, 2, 4) if ct == 4 else (1, 2))} if ksteps >= 4 and ct >= 4 else set()
+    cands = train_ops.conv_candidates(M, cin, cout)                # the list _conv_choice times, in its order
+    assert len(set(cands)) == len(cands)
+    cts = [ct for ct in (4, 6, 8) if any(c_[1] == ct for c_ in cands)]
+    if ksteps >= 8 and cts:                                    # the DMA ring wherever LDS-shared fragments are offered (K-heavy layers)
+        assert any(c_[2] == 8 and c_[0] <= 2 for c_ in cands), cands
+    if any(train_ops._stream_lds_ok(ksteps, ct) and 64 <= ksteps * ct <= 160 and (8 <= ksteps <= 20 or ksteps == 24) for ct in cts):
+        assert any(c_[:1] + c_[2:] == (2, 5) for c_ in cands), cands          # the eight-wave stream + LDS form
     assert len(cands) >= 6
     ran = 0
     co4 = -(-cout // 4) * 4                                  # the kernels store 4 channels at a time (train_ops pads odd class counts the same way)
-    for pt, ct, tk in sorted(cands):
+    for pt, ct, tk in cands:
         wp = train_ops._packed_1x1(w.contiguous(), cout, cin, 0, lib.F16, ct, x.device)
         bp = train_ops._zero_bias(x.device, -(-cout // (16 * ct)) * 16 * ct)
         out = torch.full((B, cout, H, W), float("nan"), device="cuda", dtype=torch.float16).contiguous(memory_format=torch.channels_last)
