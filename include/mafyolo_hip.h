@@ -731,6 +731,46 @@ int maf_pr_match(const float* rows, const int32_t* count, int32_t B, int32_t max
 int maf_pr_curves(const int64_t* sorted_keys, const int64_t* perm, const uint16_t* masks, int64_t capacity, const int32_t* state,
                   int32_t nc, int32_t niou, void* workspace, int64_t workspace_bytes, double* out, maf_stream_t stream);
 
+/*
+ * COCO bbox mAP (pycocotools' COCOeval, iouType 'bbox', useCats 1, as Evaler.eval_model runs it, yolov6/core/evaler.py:276-364); the rules
+ * are those of tests/cocoeval_ref.py.  Every pointer below is a DEVICE pointer; nothing synchronises the host.  T = 10 IoU thresholds,
+ * R = 101 recall thresholds, A = 4 area ranges, M = 3 maxDets (MAF_COCO_*); the parameters travel as the host's doubles.
+ *
+ * maf_coco_append: one batch of maf_coco_rows output -> detection records.  packed [rows][7] fp32 (batch image, category id, x, y, w, h,
+ *   score), total [1] int32 (rows past it are written as padding); img_index [B] int32: batch image -> gt image index; cat_lut [n_lut] int32:
+ *   category id -> category index or -1.  Per row: det_img / det_cat int32 (-1: padding / unknown category), det_box [4] fp64 =
+ *   rint(v * 1000) / 1000, det_score fp64 = rint(v * 1e5) / 1e5.
+ *
+ * maf_coco_match: one workgroup per (image, category) cell c = image * K + category.  The gt records are sorted by cell (JSON order within),
+ *   gt_off [I * K + 1]; gt_flags: MAF_COCO_GT_CROWD | MAF_COCO_GT_IDNZ (the annotation id is nonzero); at most MAF_COCO_MAX_GT per cell.
+ *   cell_keys [n] ascending (stable sort of the records by cell after a stable sort by score descending; INT64_MAX: not evaluated), order [n]:
+ *   the record index of each sorted position.  img_sel [I] uint8, cat_map [K] int32 (>= 0: evaluated).  iou_thrs [T], area_rng [A][2] fp64.
+ *   Per sorted position of the first MAF_COCO_MAX_DETS of a cell: rank (the caller fills -1 first), mbits / ibits (bit a * T + t: matched to
+ *   a gt with a nonzero id / ignored); npig [I * K][A] int32: non-ignored gts per cell and area range.
+ *
+ * maf_coco_accumulate: cat_keys [n] ascending (the evaluated category index k' of each kept position, INT64_MAX otherwise; stable sort after a
+ *   stable sort by score descending of the cell-ordered positions) with rank / mbits / ibits / score gathered in that order.  cat_of [Kp]:
+ *   k' -> category index (-1: no such category).  rec_thrs [R] fp64, max_dets [M] int32.  precision, scores [T][R][Kp][A][M] and recall
+ *   [T][Kp][A][M] fp64 are written whole (-1 where pycocotools leaves -1).
+ */
+#define MAF_COCO_T 10
+#define MAF_COCO_R 101
+#define MAF_COCO_A 4
+#define MAF_COCO_M 3
+#define MAF_COCO_MAX_DETS 100
+#define MAF_COCO_MAX_GT 256
+#define MAF_COCO_GT_CROWD 1
+#define MAF_COCO_GT_IDNZ 2
+int maf_coco_append(const float* packed, const int32_t* total, int64_t rows, const int32_t* img_index, int32_t B, const int32_t* cat_lut,
+                    int32_t n_lut, int32_t* det_img, int32_t* det_cat, double* det_box, double* det_score, maf_stream_t stream);
+int maf_coco_match(const double* gt_box, const double* gt_area, const uint8_t* gt_flags, const int64_t* gt_off, const int64_t* cell_keys,
+                   const int64_t* order, const double* det_box, int64_t n, const uint8_t* img_sel, const int32_t* cat_map, int32_t I, int32_t K,
+                   const double* iou_thrs, const double* area_rng, int32_t* rank, uint64_t* mbits, uint64_t* ibits, int32_t* npig,
+                   maf_stream_t stream);
+int maf_coco_accumulate(const int64_t* cat_keys, const int32_t* rank, const uint64_t* mbits, const uint64_t* ibits, const double* score, int64_t n,
+                        const int32_t* npig, const uint8_t* img_sel, const int32_t* cat_of, int32_t I, int32_t K, int32_t Kp,
+                        const double* rec_thrs, const int32_t* max_dets, double* precision, double* recall, double* scores, maf_stream_t stream);
+
 /* Diagnostics: shader-clock cycle stamps of image 0 of the last maf_nms call (synchronises the device):
  * [0] sort, [1] kept-list screening, [2] wave resolution, [3] total, [4] candidates, [5] survivors. */
 int maf_nms_debug(uint64_t* host8);

@@ -10,6 +10,8 @@ from .letterbox import letterbox, eval_batch, rescale_boxes, detect_frames  # no
 from .augment import TrainAugment, train_batch  # noqa: F401
 from . import metrics  # noqa: F401
 from .metrics import PrMetric  # noqa: F401
+from . import cocoeval  # noqa: F401
+from .cocoeval import CocoGt, CocoEval  # noqa: F401
 from .checkpoint import load_checkpoint, reference_state_dict  # noqa: F401
 from .loss import ComputeLoss, task_aligned_assign  # noqa: F401
 from .streams import concurrent_streams  # noqa: F401

@@ -11,6 +11,11 @@
 //   imgs = torch.ops.mafyolo.mosaic_affine(samples, samples_dev, S)     # mosaic + random_affine + mixup + augment_hsv + flips (datasets.py:147-275)
 //   torch.ops.mafyolo.pr_match(rows, count, targets, img, H, W, iouv, nc, flags, cm_conf, cm_iou, offs, i, keys, masks, state)  # evaler.py:195-238
 //   out = torch.ops.mafyolo.pr_curves(keys, masks, state, nc, niou)    # ap_per_class + the summary of evaler.py:240-268 (metrics.py:13-103)
+//   img, cat, box, score = torch.ops.mafyolo.coco_append(packed, total, img_index, cat_lut)          # COCOeval results (evaler.py:299-300)
+//   rank, mbits, ibits, npig = torch.ops.mafyolo.coco_match(gt_box, gt_area, gt_flags, gt_off, cell_keys, order, det_box, img_sel, cat_map,
+//                                                           I, K, iou_thrs, area_rng)                 # COCOeval.evaluate (evaler.py:309)
+//   precision, recall, scores = torch.ops.mafyolo.coco_accumulate(cat_keys, rank, mbits, ibits, score, npig, img_sel, cat_of, I, K,
+//                                                                 rec_thrs, max_dets)                # COCOeval.accumulate (evaler.py:310)
 //
 // Every op takes / returns at::Tensor (NCHW shape, channels_last = NHWC memory, fp16 or fp32, on the HIP device), runs on the CURRENT HIP
 // stream, allocates its outputs through the caching allocator, keeps no reference after it returns and reports errors as RuntimeError
@@ -458,6 +463,74 @@ Tensor pr_curves(const Tensor& keys, const Tensor& masks, const Tensor& state, i
     return out;
 }
 
+void check_dev(std::initializer_list<const Tensor*> ts, const char* what) {
+    for (const Tensor* t : ts)
+        TORCH_CHECK(t->is_cuda() && t->is_contiguous(), "mafyolo::", what, ": every tensor is a contiguous HIP tensor (there is no CPU path)");
+}
+
+// One batch of maf_coco_rows output -> COCOeval detection records (maf_coco_append; layout in include/mafyolo_hip.h).  packed fp32 [rows, 7],
+// total int32 [1], img_index int32 [B], cat_lut int32 [n_lut] -> (img int32, cat int32, box fp64 [rows, 4], score fp64).
+std::tuple<Tensor, Tensor, Tensor, Tensor> coco_append(const Tensor& packed, const Tensor& total, const Tensor& img_index, const Tensor& cat_lut) {
+    check_dev({&packed, &total, &img_index, &cat_lut}, "coco_append");
+    TORCH_CHECK(packed.scalar_type() == at::kFloat && packed.dim() == 2 && packed.size(1) == 7 && packed.size(0) > 0 && total.scalar_type() == at::kInt &&
+                img_index.scalar_type() == at::kInt && cat_lut.scalar_type() == at::kInt, "mafyolo::coco_append: packed fp32 [R, 7], total / img_index / cat_lut int32");
+    const c10::DeviceGuard device_guard(packed.device());
+    const int64_t R = packed.size(0);
+    Tensor img = at::empty({R}, packed.options().dtype(at::kInt)), cat = at::empty({R}, packed.options().dtype(at::kInt));
+    Tensor box = at::empty({R, 4}, packed.options().dtype(at::kDouble)), score = at::empty({R}, packed.options().dtype(at::kDouble));
+    check(maf_coco_append(packed.data_ptr<float>(), total.data_ptr<int32_t>(), R, img_index.data_ptr<int32_t>(), (int)img_index.numel(),
+                          cat_lut.data_ptr<int32_t>(), (int)cat_lut.numel(), img.data_ptr<int32_t>(), cat.data_ptr<int32_t>(), box.data_ptr<double>(),
+                          score.data_ptr<double>(), stream_of(packed)), "coco_append");
+    return {img, cat, box, score};
+}
+
+// evaluateImg over every (image, category) cell (maf_coco_match) -> (rank int32 [n], mbits / ibits int64 [n], npig int32 [I * K, 4]).
+std::tuple<Tensor, Tensor, Tensor, Tensor> coco_match(const Tensor& gt_box, const Tensor& gt_area, const Tensor& gt_flags, const Tensor& gt_off,
+                                                      const Tensor& cell_keys, const Tensor& order, const Tensor& det_box, const Tensor& img_sel,
+                                                      const Tensor& cat_map, int64_t I, int64_t K, const Tensor& iou_thrs, const Tensor& area_rng) {
+    check_dev({&gt_box, &gt_area, &gt_flags, &gt_off, &cell_keys, &order, &det_box, &img_sel, &cat_map, &iou_thrs, &area_rng}, "coco_match");
+    TORCH_CHECK(gt_box.scalar_type() == at::kDouble && gt_area.scalar_type() == at::kDouble && gt_flags.scalar_type() == at::kByte &&
+                gt_off.scalar_type() == at::kLong && gt_off.numel() == I * K + 1 && cell_keys.scalar_type() == at::kLong &&
+                order.scalar_type() == at::kLong && order.numel() == cell_keys.numel() && det_box.scalar_type() == at::kDouble &&
+                img_sel.scalar_type() == at::kByte && img_sel.numel() == I && cat_map.scalar_type() == at::kInt && cat_map.numel() == K &&
+                iou_thrs.scalar_type() == at::kDouble && iou_thrs.numel() == MAF_COCO_T && area_rng.scalar_type() == at::kDouble &&
+                area_rng.numel() == 2 * MAF_COCO_A, "mafyolo::coco_match: tensor types / shapes (include/mafyolo_hip.h)");
+    const c10::DeviceGuard device_guard(det_box.device());
+    const int64_t n = cell_keys.numel();
+    Tensor rank = at::full({n}, -1, det_box.options().dtype(at::kInt));
+    Tensor mbits = at::zeros({n}, det_box.options().dtype(at::kLong)), ibits = at::zeros({n}, det_box.options().dtype(at::kLong));
+    Tensor npig = at::empty({I * K, MAF_COCO_A}, det_box.options().dtype(at::kInt));
+    check(maf_coco_match(gt_box.data_ptr<double>(), gt_area.data_ptr<double>(), gt_flags.data_ptr<uint8_t>(), gt_off.data_ptr<int64_t>(),
+                         cell_keys.data_ptr<int64_t>(), order.data_ptr<int64_t>(), det_box.data_ptr<double>(), n, img_sel.data_ptr<uint8_t>(),
+                         cat_map.data_ptr<int32_t>(), (int)I, (int)K, iou_thrs.data_ptr<double>(), area_rng.data_ptr<double>(), rank.data_ptr<int32_t>(),
+                         reinterpret_cast<uint64_t*>(mbits.data_ptr<int64_t>()), reinterpret_cast<uint64_t*>(ibits.data_ptr<int64_t>()),
+                         npig.data_ptr<int32_t>(), stream_of(det_box)), "coco_match");
+    return {rank, mbits, ibits, npig};
+}
+
+// accumulate (maf_coco_accumulate) on the kept records in (category, score descending) order -> precision, scores fp64 [T, R, Kp, A, M],
+// recall fp64 [T, Kp, A, M] with -1 where pycocotools leaves -1.
+std::tuple<Tensor, Tensor, Tensor> coco_accumulate(const Tensor& cat_keys, const Tensor& rank, const Tensor& mbits, const Tensor& ibits, const Tensor& score,
+                                                   const Tensor& npig, const Tensor& img_sel, const Tensor& cat_of, int64_t I, int64_t K,
+                                                   const Tensor& rec_thrs, const Tensor& max_dets) {
+    check_dev({&cat_keys, &rank, &mbits, &ibits, &score, &npig, &img_sel, &cat_of, &rec_thrs, &max_dets}, "coco_accumulate");
+    const int64_t n = cat_keys.numel(), Kp = cat_of.numel();
+    TORCH_CHECK(cat_keys.scalar_type() == at::kLong && rank.scalar_type() == at::kInt && rank.numel() == n && mbits.scalar_type() == at::kLong &&
+                mbits.numel() == n && ibits.scalar_type() == at::kLong && ibits.numel() == n && score.scalar_type() == at::kDouble && score.numel() == n &&
+                npig.scalar_type() == at::kInt && npig.numel() == I * K * MAF_COCO_A && img_sel.scalar_type() == at::kByte && img_sel.numel() == I &&
+                cat_of.scalar_type() == at::kInt && Kp > 0 && rec_thrs.scalar_type() == at::kDouble && rec_thrs.numel() == MAF_COCO_R &&
+                max_dets.scalar_type() == at::kInt && max_dets.numel() == MAF_COCO_M, "mafyolo::coco_accumulate: tensor types / shapes (include/mafyolo_hip.h)");
+    const c10::DeviceGuard device_guard(score.device());
+    Tensor precision = at::empty({MAF_COCO_T, MAF_COCO_R, Kp, MAF_COCO_A, MAF_COCO_M}, score.options());
+    Tensor scores = at::empty_like(precision), recall = at::empty({MAF_COCO_T, Kp, MAF_COCO_A, MAF_COCO_M}, score.options());
+    check(maf_coco_accumulate(cat_keys.data_ptr<int64_t>(), rank.data_ptr<int32_t>(), reinterpret_cast<const uint64_t*>(mbits.data_ptr<int64_t>()),
+                              reinterpret_cast<const uint64_t*>(ibits.data_ptr<int64_t>()), score.data_ptr<double>(), n, npig.data_ptr<int32_t>(),
+                              img_sel.data_ptr<uint8_t>(), cat_of.data_ptr<int32_t>(), (int)I, (int)K, (int)Kp, rec_thrs.data_ptr<double>(),
+                              max_dets.data_ptr<int32_t>(), precision.data_ptr<double>(), recall.data_ptr<double>(), scores.data_ptr<double>(),
+                              stream_of(score)), "coco_accumulate");
+    return {precision, recall, scores};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(mafyolo, m) {
@@ -480,6 +553,11 @@ TORCH_LIBRARY(mafyolo, m) {
     m.def("pr_match(Tensor rows, Tensor count, Tensor targets, Tensor img_params, int H, int W, Tensor iouv, int nc, int flags, float cm_conf, "
           "float cm_iou, Tensor(a!) offs, int batch, Tensor(b!) keys, Tensor(c!) masks, Tensor(d!) state) -> ()");
     m.def("pr_curves(Tensor keys, Tensor masks, Tensor state, int nc, int niou) -> Tensor");
+    m.def("coco_append(Tensor packed, Tensor total, Tensor img_index, Tensor cat_lut) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("coco_match(Tensor gt_box, Tensor gt_area, Tensor gt_flags, Tensor gt_off, Tensor cell_keys, Tensor order, Tensor det_box, "
+          "Tensor img_sel, Tensor cat_map, int I, int K, Tensor iou_thrs, Tensor area_rng) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("coco_accumulate(Tensor cat_keys, Tensor rank, Tensor mbits, Tensor ibits, Tensor score, Tensor npig, Tensor img_sel, Tensor cat_of, "
+          "int I, int K, Tensor rec_thrs, Tensor max_dets) -> (Tensor, Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(mafyolo, CUDA, m) {       // the HIP device is the "CUDA" dispatch key of PyTorch-ROCm
@@ -501,4 +579,7 @@ TORCH_LIBRARY_IMPL(mafyolo, CUDA, m) {       // the HIP device is the "CUDA" dis
     m.impl("mosaic_affine", &mosaic_affine);
     m.impl("pr_match", &pr_match);
     m.impl("pr_curves", &pr_curves);
+    m.impl("coco_append", &coco_append);
+    m.impl("coco_match", &coco_match);
+    m.impl("coco_accumulate", &coco_accumulate);
 }

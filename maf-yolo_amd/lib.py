@@ -67,6 +67,10 @@ PR_MAX_CLASSES = 1024
 PR_HEADER = 16                # MAF_PR_HEADER: fp64 summary slots at the start of maf_pr_curves' output
 PR_LABELS_XYXY, PR_CONFUSION = 1, 2
 PR_ERR_CLASS, PR_ERR_LABELS, PR_ERR_CAPACITY = 1, 2, 4
+COCO_T, COCO_R, COCO_A, COCO_M = 10, 101, 4, 3   # MAF_COCO_*: the shape of COCOeval's bbox defaults
+COCO_MAX_DETS = 100           # MAF_COCO_MAX_DETS: maxDets[-1], detections kept per (image, category) cell
+COCO_MAX_GT = 256             # MAF_COCO_MAX_GT: gts one (image, category) cell may hold
+COCO_GT_CROWD, COCO_GT_IDNZ = 1, 2
 
 
 class MafEmaDesc(C.Structure):
@@ -120,6 +124,7 @@ EXPORTS = ["maf_last_error", "maf_version", "maf_op_size", "maf_op_launch", "maf
            "maf_stream_create_masked", "maf_stream_destroy", "maf_letterbox", "maf_letterbox_lds_bytes", "maf_rescale_boxes",
            "maf_augment_resize", "maf_mosaic_affine", "maf_augment_sample_size",
            "maf_pr_state_ints", "maf_pr_out_doubles", "maf_pr_workspace_bytes", "maf_pr_match", "maf_pr_curves",
+           "maf_coco_append", "maf_coco_match", "maf_coco_accumulate",
            "maf_timer_create", "maf_timer_start", "maf_timer_stop", "maf_timer_elapsed_ms", "maf_timer_destroy"]
 
 _lib = None
@@ -281,6 +286,14 @@ def load():
                                  C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.maf_pr_curves.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                   C.c_void_p, C.c_void_p]
+    lib.maf_coco_append.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.maf_coco_match.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                   C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]
+    lib.maf_coco_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]
     lib.maf_timer_create.argtypes = [C.POINTER(C.c_void_p)]
     lib.maf_timer_start.argtypes = [C.c_void_p, C.c_void_p]
     lib.maf_timer_stop.argtypes = [C.c_void_p, C.c_void_p]

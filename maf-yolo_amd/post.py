@@ -53,6 +53,11 @@ def convert_to_coco_format(outputs, imgs, paths, shapes, ids, is_coco=True, scal
             rows[b, :o.shape[0]] = o.float()
         count = torch.tensor([int(o.shape[0]) for o in outputs], dtype=torch.int32, device=dev)
     packed, total = coco_rows(rows, count, shapes, ids, scale_exact)
+    return coco_results(packed, total, paths, is_coco)
+
+
+def coco_results(packed, total, paths, is_coco=True):
+    """Host part: coco_rows' (packed, total) of one batch -> the reference's list of dicts."""
     n = int(total.item())                                   # the one host sync
     arr = packed[:n].cpu().numpy().astype(np.float64)
     bbox = np.round(arr[:, 2:6] * 1000.0) / 1000.0          # == round(v, 3) for doubles that come from fp32: v * 1000 is exact

@@ -11,6 +11,9 @@
     imgs = ops.mosaic_affine(samples, samples_dev, 640)            # the pixels of TrainValDataset.__getitem__ (datasets.py:147-275); maf_yolo_amd.train_batch
     ops.pr_match(rows, count, targets, img, H, W, iouv, nc, flags, 0.25, 0.45, offs, i, keys, masks, state)  # evaler.py:195-238; metrics.PrMetric.update
     out = ops.pr_curves(keys, masks, state, nc, niou)               # ap_per_class + the summary (evaler.py:240-268); metrics.PrMetric.compute
+    img, cat, box, score = ops.coco_append(packed, total, img_index, cat_lut)        # COCOeval results; cocoeval.CocoEval.update
+    rank, mbits, ibits, npig = ops.coco_match(...)                  # COCOeval.evaluate (evaler.py:309); cocoeval.CocoEval.evaluate
+    precision, recall, scores = ops.coco_accumulate(...)            # COCOeval.accumulate (evaler.py:310); cocoeval.CocoEval.accumulate
     dets = torch_ops.non_max_suppression(pred, 0.03, 0.65, multi_label=True)    # ... as the reference's list of [n_i, 6] tensors
 
 The C++ side (csrc/torch_ops.cpp) defines the schemas and the HIP ("CUDA" dispatch key) implementations, which marshal at::Tensor into
@@ -32,7 +35,7 @@ ACT_NONE, ACT_RELU, ACT_SILU, ACT_SIGMOID = lib.ACT_NONE, lib.ACT_RELU, lib.ACT_
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libmafyolo_torch.so")
 OPS = ("conv1x1_bias_act", "conv3x3s2_bias_act", "dwconv_bias_act", "conv1x1_dgrad", "conv3x3s2_dgrad", "conv_wgrad", "dwconv_dgrad", "dwconv_wgrad",
        "head_decode", "decode_nms", "mprep", "sppf", "bn_act", "bn_act_backward", "letterbox", "mosaic_affine",
-       "pr_match", "pr_curves")
+       "pr_match", "pr_curves", "coco_append", "coco_match", "coco_accumulate")
 _registered = False
 
 
@@ -105,6 +108,24 @@ def _register():
     @L.register_fake("mafyolo::pr_curves")
     def _(keys, masks, state, nc, niou):
         return keys.new_empty((lib.PR_HEADER + 4000 * nc + nc * niou + nc + (nc + 1) ** 2,), dtype=torch.float64)
+
+    @L.register_fake("mafyolo::coco_append")
+    def _(packed, total, img_index, cat_lut):
+        R = packed.shape[0]
+        return (packed.new_empty((R,), dtype=torch.int32), packed.new_empty((R,), dtype=torch.int32),
+                packed.new_empty((R, 4), dtype=torch.float64), packed.new_empty((R,), dtype=torch.float64))
+
+    @L.register_fake("mafyolo::coco_match")
+    def _(gt_box, gt_area, gt_flags, gt_off, cell_keys, order, det_box, img_sel, cat_map, I, K, iou_thrs, area_rng):
+        n = cell_keys.shape[0]
+        return (det_box.new_empty((n,), dtype=torch.int32), det_box.new_empty((n,), dtype=torch.int64),
+                det_box.new_empty((n,), dtype=torch.int64), det_box.new_empty((I * K, lib.COCO_A), dtype=torch.int32))
+
+    @L.register_fake("mafyolo::coco_accumulate")
+    def _(cat_keys, rank, mbits, ibits, score, npig, img_sel, cat_of, I, K, rec_thrs, max_dets):
+        Kp = cat_of.shape[0]
+        p = score.new_empty((lib.COCO_T, lib.COCO_R, Kp, lib.COCO_A, lib.COCO_M))
+        return p, score.new_empty((lib.COCO_T, Kp, lib.COCO_A, lib.COCO_M)), p.new_empty(p.shape)
 
     @L.register_fake("mafyolo::mprep")
     def _(x, w1, b1, w3, b3):
