@@ -771,6 +771,69 @@ int maf_coco_accumulate(const int64_t* cat_keys, const int32_t* rank, const uint
                         const int32_t* npig, const uint8_t* img_sel, const int32_t* cat_of, int32_t I, int32_t K, int32_t Kp,
                         const double* rec_thrs, const int32_t* max_dets, double* precision, double* recall, double* scores, maf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------------------
+ * Baseline JPEG decoding on the device (csrc/jpeg_decode.hip): what cv2.imread (libjpeg with its defaults: JDCT_ISLOW, fancy upsampling,
+ * BGR) returns for a file, bit for bit; the rules are those of tests/jpeg_ref.py.  SOF0, 8 bit, Huffman, one interleaved scan, 1 or 3
+ * components (Y 1x1, 2x1 or 2x2 with 1x1 chroma).  The host walks the markers (maf-yolo_amd/jpeg.py) and hands over ONE byte blob, copied
+ * to the device as it is: maf_jpeg_header_t | maf_jpeg_image_t [n_images] | maf_jpeg_lane_t [n_lanes] | Huffman table sets | quantisation
+ * tables (uint16 [3][64] per image, natural order) | the scans' bytes followed by at least MAF_JPEG_SCAN_PAD zero bytes.
+ *
+ * Stages of a call (one chain of launches on `stream`, nothing synchronises; `stages` selects them, MAF_JPEG_STAGE_ALL for a decode):
+ *   ENTROPY  jdhuff.c decode_mcu: one lane per restart interval (per image without DRI), `group` lanes per one-wave workgroup sharing one
+ *            Huffman table set in LDS; 0xFF00 unstuffed on the fly; DC prediction reset per lane and component; int16 coefficients in
+ *            natural order (jutils.c jpeg_natural_order) for every block of every MCU (jdcoefct.c), component after component, blocks
+ *            row-major over the component padded to whole MCUs.  The reader's byte index is clamped into the scan buffer, so no stream
+ *            content reads or writes outside the buffers; faults set bits of status[image] (MAF_JPEG_ST_*) instead.
+ *   IDCT     jidctint.c jpeg_idct_islow with dequantisation and the range-limit table of jdmaster.c -> uint8 component planes padded to
+ *            whole MCUs (pitch 8 * blocks per row).
+ *   COLOR    jdsample.c h2v1_fancy_upsample / h2v2_fancy_upsample (the box replication of h2v1_upsample / h2v2_upsample where the chroma
+ *            plane is at most 2 samples wide), the edge rules of jdmainct.c, jdcolor.c ycc_rgb_convert's 16-bit tables -> uint8 [h][w][3]
+ *            BGR at out + out_off; a one-component file writes its gray value three times.
+ *
+ * A Huffman table set is 4 tables (DC 0, DC 1, AC 0, AC 1) of MAF_JPEG_HUFF_TABLE_BYTES: look uint16 [512] (length << 8 | symbol for every
+ * 9-bit prefix that starts with a code of at most 9 bits, else 0), maxcode int32 [18] (-1: no code of that length), valoff int32 [18]
+ * (symbol = huffval[valoff[l] + code]), huffval uint8 [256].  Lanes [group g, group (g + 1)) share one tabset; padding lanes have image -1.
+ * maf_jpeg_decode validates the whole HOST copy of the blob (every offset, size and index) before it touches the device.
+ */
+#define MAF_JPEG_GROUP 64
+#define MAF_JPEG_SCAN_PAD 64
+#define MAF_JPEG_HUFF_TABLE_BYTES 1424
+#define MAF_JPEG_ST_BAD_CODE 1      /* no Huffman code matches, or a DC category above 16 */
+#define MAF_JPEG_ST_BAD_INDEX 2     /* an AC run moves past coefficient 63 */
+#define MAF_JPEG_ST_SHORT_SCAN 4    /* the interval's bytes ran out before its MCUs did */
+#define MAF_JPEG_STAGE_ENTROPY 1
+#define MAF_JPEG_STAGE_IDCT 2
+#define MAF_JPEG_STAGE_COLOR 4
+#define MAF_JPEG_STAGE_ALL 7
+typedef struct {
+    int32_t n_images, n_lanes, n_tabsets;
+    int32_t group;                           /* decoding lanes per workgroup, 1 to MAF_JPEG_GROUP; n_lanes is a multiple of it */
+    int64_t images_off, lanes_off, huff_off, quant_off, scan_off;   /* byte offsets of the sections in the blob (16-byte aligned) */
+    int64_t scan_bytes;                      /* the scans' bytes including the zero padding */
+    int64_t total_bytes;                     /* of the blob */
+    int64_t coef_elems, plane_bytes, out_bytes;   /* sizes of the three device buffers */
+} maf_jpeg_header_t;
+typedef struct {
+    int64_t coef_off;                        /* int16 elements, a multiple of 64 */
+    int64_t plane_off;                       /* bytes, a multiple of 64 */
+    int64_t out_off;                         /* bytes, a multiple of 16 */
+    int32_t w, h, ncomp;                     /* ncomp 1 or 3 */
+    int32_t hs, vs;                          /* luma sampling factors (1,1), (2,1) or (2,2); chroma is 1 x 1 */
+    int32_t mcux, mcuy;                      /* ceil(w / (8 hs)), ceil(h / (8 vs)) */
+    int32_t quant;                           /* index of the image's first quantisation table */
+    int32_t dc_tab[3], ac_tab[3];            /* per component: table 0 or 1 of the set */
+    int32_t reserved[2];
+} maf_jpeg_image_t;
+typedef struct {
+    int64_t begin, end;                      /* byte range of the interval inside the scan buffer (markers excluded) */
+    int32_t image;                           /* -1: a padding lane */
+    int32_t first_mcu, n_mcu;
+    int32_t tabset;
+} maf_jpeg_lane_t;
+int maf_jpeg_struct_sizes(int32_t* header_image_lane);   /* sizeof of the three structs above (binding check) */
+int maf_jpeg_decode(const void* blob_host, const void* blob_dev, int16_t* coef, uint8_t* planes, uint8_t* out, int32_t* status,
+                    int32_t stages, maf_stream_t stream);
+
 /* Diagnostics: shader-clock cycle stamps of image 0 of the last maf_nms call (synchronises the device):
  * [0] sort, [1] kept-list screening, [2] wave resolution, [3] total, [4] candidates, [5] survivors. */
 int maf_nms_debug(uint64_t* host8);

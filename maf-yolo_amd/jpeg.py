@@ -1,0 +1,468 @@
+"""File bytes in, frames out, on the device: baseline JPEG decoding that equals libjpeg's defaults (what cv2.imread returns) bit for bit.
+
+The stage in front of letterbox.py / augment.py that the reference runs on the host, one file at a time, through cv2.imread
+(yolov6/data/datasets.py load_image, LoadData of yolov6/core/inferer.py):
+  * parse(data)       host only: walks the markers of one file -> JpegInfo (size, components, tables, restart interval, the scan's byte
+                      range, EXIF orientation).  JpegUnsupported names everything outside the supported set, MafError a malformed file;
+  * supported(data)   True where decode() takes the file (a caller routes the others to the host decoder);
+  * decode(files)     a list of bytes-like objects or paths -> a list of uint8 [h_i, w_i, 3] BGR CUDA tensors: ONE pinned staging buffer, ONE
+                      host -> device copy, one chain of launches for the whole call (csrc/jpeg_decode.hip: entropy decode, dequantise +
+                      islow IDCT, fancy upsampling + YCbCr -> BGR), no host synchronisation unless check=True reads the status words.
+Supported: baseline sequential DCT (SOF0), 8 bit, Huffman, one interleaved scan, 1 component or 3 (Y 1x1, 2x1 or 2x2 with 1x1 chroma).
+The pixels follow libjpeg's JDCT_ISLOW + fancy upsampling + jdcolor.c tables as restated in tests/jpeg_ref.py.  cv2.imread also rotates by
+the EXIF orientation; this decoder does not, so such a file raises JpegUnsupported unless ignore_orientation=True.  No CPU fallback.
+"""
+import os
+import struct
+from collections import namedtuple
+
+import numpy as np
+
+from . import lib
+from .lib import MafError
+
+
+class JpegUnsupported(MafError):
+    """A well-formed JPEG file outside the supported set (the message names the kind)."""
+
+
+JpegComponent = namedtuple("JpegComponent", "id h v tq td ta")
+JpegInfo = namedtuple("JpegInfo", "width height precision components qtables huffman restart_interval scan orientation adobe_transform")
+# qtables: {id: uint16 [64] in natural (row-major) order}; huffman: {(class, id): (bits uint8 [16], values uint8 [n])}, class 0 = DC, 1 = AC;
+# scan: (first byte, one past the last byte) of the entropy-coded segment, RST markers included; orientation: the EXIF tag or None
+
+# jpeg_natural_order of jutils.c: zigzag position -> row-major position
+ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                   35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63],
+                  np.int64)
+
+STATUS_BAD_CODE, STATUS_BAD_INDEX, STATUS_SHORT_SCAN = 1, 2, 4      # MAF_JPEG_ST_*: bits of a per-image status word
+_STATUS_TEXT = ((STATUS_BAD_CODE, "an invalid Huffman code"), (STATUS_BAD_INDEX, "a coefficient index past 63"),
+                (STATUS_SHORT_SCAN, "a scan that ends early"))
+
+_SOF_NAMES = {0xC1: "extended sequential DCT (SOF1)", 0xC2: "progressive DCT (SOF2)", 0xC3: "lossless (SOF3)",
+              0xC5: "differential sequential DCT (SOF5)", 0xC6: "differential progressive DCT (SOF6)", 0xC7: "differential lossless (SOF7)",
+              0xC9: "arithmetic coding (SOF9)", 0xCA: "arithmetic coding (SOF10, progressive)", 0xCB: "arithmetic coding (SOF11, lossless)",
+              0xCD: "arithmetic coding (SOF13)", 0xCE: "arithmetic coding (SOF14)", 0xCF: "arithmetic coding (SOF15)"}
+
+
+def _bytes(data):
+    if isinstance(data, (str, os.PathLike)):
+        with open(data, "rb") as f:
+            return f.read()
+    return bytes(data)
+
+
+def _exif_orientation(seg):
+    """The orientation tag (0x0112) of IFD0 of an APP1 Exif segment, or None."""
+    if len(seg) < 14 or seg[:6] != b"Exif\x00\x00":
+        return None
+    t = seg[6:]
+    if t[:2] == b"II":
+        e = "<"
+    elif t[:2] == b"MM":
+        e = ">"
+    else:
+        return None
+    if struct.unpack(e + "H", t[2:4])[0] != 42:
+        return None
+    off = struct.unpack(e + "I", t[4:8])[0]
+    if off + 2 > len(t):
+        return None
+    n = struct.unpack(e + "H", t[off:off + 2])[0]
+    for i in range(n):
+        p = off + 2 + 12 * i
+        if p + 12 > len(t):
+            return None
+        tag, typ, cnt = struct.unpack(e + "HHI", t[p:p + 8])
+        if tag == 0x0112 and typ == 3 and cnt == 1:
+            return struct.unpack(e + "H", t[p + 8:p + 10])[0]
+    return None
+
+
+def parse(data):
+    """Walk the markers of one JPEG file (bytes-like or a path) -> JpegInfo.  Host only."""
+    d = _bytes(data)
+    n = len(d)
+    if n < 4 or d[0] != 0xFF or d[1] != 0xD8:
+        raise MafError("jpeg: no SOI marker at the start (not a JPEG file)")
+    qt, huff = {}, {}
+    frame = None
+    restart = 0
+    orientation = None
+    adobe = None
+    p = 2
+    while True:
+        if p + 2 > n:
+            raise MafError("jpeg: the file ends before a scan (no SOS marker)")
+        if d[p] != 0xFF:
+            raise MafError("jpeg: expected a marker at byte %d" % p)
+        m = d[p + 1]
+        if m == 0xFF:                                       # fill byte
+            p += 1
+            continue
+        p += 2
+        if m == 0xD9:
+            raise MafError("jpeg: EOI before any scan")
+        if m == 0x01 or 0xD0 <= m <= 0xD7:                  # stand-alone markers
+            continue
+        if p + 2 > n:
+            raise MafError("jpeg: a segment length runs past the end of the file")
+        L = (d[p] << 8) | d[p + 1]
+        seg = d[p + 2:p + L]
+        short = L < 2 or p + L > n                          # judged after the fields that name an unsupported kind have been read
+        if m == 0xCC:
+            raise JpegUnsupported("jpeg: arithmetic coding (DAC marker) is not supported")
+        if m in _SOF_NAMES:
+            raise JpegUnsupported("jpeg: %s is not supported (baseline SOF0 only)" % _SOF_NAMES[m])
+        if m == 0xC0:
+            if len(seg) < 6:
+                raise MafError("jpeg: the SOF0 segment runs past the end of the file")
+            prec, h, w, nf = seg[0], (seg[1] << 8) | seg[2], (seg[3] << 8) | seg[4], seg[5]
+            if prec != 8:
+                raise JpegUnsupported("jpeg: %d-bit samples are not supported (8-bit only)" % prec)
+            if nf not in (1, 3):
+                raise JpegUnsupported("jpeg: %d components are not supported (1 or 3)" % nf)
+            if short or len(seg) < 6 + 3 * nf:
+                raise MafError("jpeg: the SOF0 segment runs past the end of the file")
+            if frame is not None:
+                raise MafError("jpeg: a second SOF marker")
+            if h == 0 or w == 0:
+                raise JpegUnsupported("jpeg: a frame height of 0 (DNL marker) is not supported" if w else "jpeg: zero width")
+            frame = (w, h, [(seg[6 + 3 * i], seg[7 + 3 * i] >> 4, seg[7 + 3 * i] & 15, seg[8 + 3 * i]) for i in range(nf)])
+        elif m == 0xDB:
+            q = 0
+            while q < len(seg):
+                pq, tq = seg[q] >> 4, seg[q] & 15
+                if pq != 0:
+                    raise JpegUnsupported("jpeg: 16-bit quantisation tables are not supported")
+                if short or q + 65 > len(seg):
+                    raise MafError("jpeg: a DQT segment runs past the end of the file")
+                t = np.zeros(64, np.uint16)
+                t[ZIGZAG] = np.frombuffer(seg, np.uint8, 64, q + 1)
+                qt[tq] = t
+                q += 65
+        elif m == 0xC4:
+            q = 0
+            if short:
+                raise MafError("jpeg: a DHT segment runs past the end of the file")
+            while q < len(seg):
+                if q + 17 > len(seg):
+                    raise MafError("jpeg: a DHT segment is cut short")
+                tc, th = seg[q] >> 4, seg[q] & 15
+                bits = np.frombuffer(seg, np.uint8, 16, q + 1).copy()
+                cnt = int(bits.sum())
+                if tc > 1 or cnt > 256 or q + 17 + cnt > len(seg):
+                    raise MafError("jpeg: a malformed DHT segment")
+                huff[(tc, th)] = (bits, np.frombuffer(seg, np.uint8, cnt, q + 17).copy())
+                q += 17 + cnt
+        elif m == 0xDD:
+            if short or len(seg) < 2:
+                raise MafError("jpeg: the DRI segment runs past the end of the file")
+            restart = (seg[0] << 8) | seg[1]
+        elif m == 0xE1:
+            if short:
+                raise MafError("jpeg: an APP1 segment runs past the end of the file")
+            o = _exif_orientation(seg)
+            orientation = o if o is not None else orientation
+        elif m == 0xEE:
+            if short:
+                raise MafError("jpeg: an APP14 segment runs past the end of the file")
+            if len(seg) >= 12 and seg[:5] == b"Adobe":
+                adobe = seg[11]
+        elif m == 0xDA:
+            if frame is None:
+                raise MafError("jpeg: SOS before SOF")
+            if len(seg) < 1:
+                raise MafError("jpeg: the SOS segment runs past the end of the file")
+            ns = seg[0]
+            if ns != len(frame[2]):
+                raise JpegUnsupported("jpeg: more than one scan (a scan of %d of the %d components) is not supported" % (ns, len(frame[2])))
+            if short or len(seg) < 4 + 2 * ns:
+                raise MafError("jpeg: the SOS segment runs past the end of the file")
+            comps = []
+            for i, (cid, ch, cv, tq) in enumerate(frame[2]):
+                if seg[1 + 2 * i] != cid:
+                    raise JpegUnsupported("jpeg: a scan whose component order differs from the frame's is not supported")
+                comps.append(JpegComponent(cid, ch, cv, tq, seg[2 + 2 * i] >> 4, seg[2 + 2 * i] & 15))
+            ss, se, a = seg[1 + 2 * ns], seg[2 + 2 * ns], seg[3 + 2 * ns]
+            if (ss, se, a) != (0, 63, 0):
+                raise JpegUnsupported("jpeg: a scan with spectral selection or successive approximation (progressive) is not supported")
+            p += L
+            break
+        elif short:
+            raise MafError("jpeg: a segment (marker 0xFF%02X) runs past the end of the file" % m)
+        p += L
+    w, h, _ = frame
+    # sampling: 1 component (its factors are irrelevant in a non-interleaved scan) or Y 1x1 / 2x1 / 2x2 with 1x1 chroma
+    if len(comps) == 3:
+        y, cb, cr = comps
+        if (cb.h, cb.v, cr.h, cr.v) != (1, 1, 1, 1) or (y.h, y.v) not in ((1, 1), (2, 1), (2, 2)):
+            raise JpegUnsupported("jpeg: sampling %s is not supported (Y 1x1, 2x1 or 2x2 with 1x1 chroma)"
+                                  % ", ".join("%dx%d" % (c.h, c.v) for c in comps))
+        if adobe == 0 or bytes(c.id for c in comps) == b"RGB":
+            raise JpegUnsupported("jpeg: an RGB (untransformed) colour space is not supported (YCbCr only)")
+    for c in comps:
+        if c.tq not in qt:
+            raise MafError("jpeg: quantisation table %d is missing" % c.tq)
+        if c.td > 1 or c.ta > 1:
+            raise JpegUnsupported("jpeg: Huffman table selectors above 1 (not baseline) are not supported")
+        if (0, c.td) not in huff or (1, c.ta) not in huff:
+            raise MafError("jpeg: Huffman table DC %d / AC %d is missing" % (c.td, c.ta))
+    # the entropy-coded segment ends at the first marker that is neither a stuffed 0xFF00 nor RSTn (nor a fill 0xFF)
+    a = np.frombuffer(d, np.uint8, n - p, p)
+    nxt = a[1:]
+    hit = np.flatnonzero((a[:-1] == 0xFF) & (nxt != 0) & (nxt != 0xFF) & ((nxt < 0xD0) | (nxt > 0xD7)))
+    if hit.size == 0:
+        raise MafError("jpeg: no EOI marker after the scan")
+    end = p + int(hit[0])
+    m = d[end + 1]
+    if m == 0xDA or m == 0xC4 or m == 0xDB or m == 0xDD:
+        raise JpegUnsupported("jpeg: more than one scan is not supported")
+    if m == 0xDC:
+        raise JpegUnsupported("jpeg: a DNL marker is not supported")
+    if m != 0xD9:
+        raise MafError("jpeg: marker 0xFF%02X after the scan where EOI should be" % m)
+    return JpegInfo(w, h, 8, tuple(comps), qt, huff, restart, (p, end), orientation, adobe)
+
+
+def supported(data):
+    """True where decode() takes this file: a baseline JPEG of the supported set without an EXIF rotation."""
+    try:
+        return parse(data).orientation in (None, 1)
+    except MafError:
+        return False
+
+
+# ---------------------------------------------------------------- device tables (host side)
+
+HUFF_LOOK_BITS = 9            # MAF_JPEG_LOOK_BITS: codes up to this length resolve in one table read
+HUFF_TABLE_BYTES = 2 * (1 << HUFF_LOOK_BITS) + 4 * 18 + 4 * 18 + 256      # look u16 [512] | maxcode i32 [18] | valoff i32 [18] | huffval u8 [256]
+HUFF_SET_BYTES = 4 * HUFF_TABLE_BYTES                                     # DC 0, DC 1, AC 0, AC 1
+MAX_GROUP = 64                # MAF_JPEG_GROUP: the most decoding lanes of one workgroup (one wave); they share one set of Huffman tables
+WAVE_SLOTS = 2048             # 256 CUs x 8: while the chip has free slots a wave carries one lane (the lanes of a wave diverge and serialise)
+
+IMAGE_DT = np.dtype([("coef_off", "<i8"), ("plane_off", "<i8"), ("out_off", "<i8"), ("w", "<i4"), ("h", "<i4"), ("ncomp", "<i4"), ("hs", "<i4"),
+                     ("vs", "<i4"), ("mcux", "<i4"), ("mcuy", "<i4"), ("quant", "<i4"), ("dc_tab", "<i4", 3), ("ac_tab", "<i4", 3),
+                     ("reserved", "<i4", 2)])              # maf_jpeg_image_t
+LANE_DT = np.dtype([("begin", "<i8"), ("end", "<i8"), ("image", "<i4"), ("first_mcu", "<i4"), ("n_mcu", "<i4"), ("tabset", "<i4")])   # maf_jpeg_lane_t
+HEADER_DT = np.dtype([("n_images", "<i4"), ("n_lanes", "<i4"), ("n_tabsets", "<i4"), ("group", "<i4"), ("images_off", "<i8"), ("lanes_off", "<i8"),
+                      ("huff_off", "<i8"), ("quant_off", "<i8"), ("scan_off", "<i8"), ("scan_bytes", "<i8"), ("total_bytes", "<i8"),
+                      ("coef_elems", "<i8"), ("plane_bytes", "<i8"), ("out_bytes", "<i8")])               # maf_jpeg_header_t
+SCAN_PAD = 64                 # zero bytes the host appends to the scan buffer (the bit reader's clamp lands in them)
+STAGE_ENTROPY, STAGE_IDCT, STAGE_COLOR, STAGE_ALL = 1, 2, 4, 7
+
+
+def huff_device_table(bits, vals):
+    """One Huffman table in the layout the entropy kernel keeps in LDS (jpeg_make_d_derived_tbl of jdhuff.c, with a 9-bit lookahead):
+    look[c] = length << 8 | symbol for every 9-bit prefix c that starts with a code of at most 9 bits, else 0; for longer codes
+    maxcode[l] (-1: no code of length l) and valoff[l] with symbol = huffval[valoff[l] + code]."""
+    out = np.zeros(HUFF_TABLE_BYTES, np.uint8)
+    look = out[:1024].view("<u2")
+    maxcode = out[1024:1096].view("<i4")
+    valoff = out[1096:1168].view("<i4")
+    out[1168:1168 + len(vals)] = vals
+    maxcode[:] = -1
+    code, k = 0, 0
+    for l in range(1, 17):
+        nl = int(bits[l - 1])
+        if nl:
+            if code + nl > (1 << l):
+                raise MafError("jpeg: a Huffman table assigns more codes than its lengths allow")
+            valoff[l] = k - code
+            if l <= HUFF_LOOK_BITS:
+                for i in range(nl):
+                    c = (code + i) << (HUFF_LOOK_BITS - l)
+                    look[c:c + (1 << (HUFF_LOOK_BITS - l))] = (l << 8) | int(vals[k + i])
+            code += nl
+            k += nl
+            maxcode[l] = code - 1
+        code <<= 1
+    maxcode[17] = 0xFFFFF                                   # jdhuff.c's sentinel: ends the search
+    return out
+
+
+def _restart_ranges(d, scan, n_lanes):
+    """Byte ranges of the restart intervals inside the scan (RST markers excluded) -> [(begin, end)] * n_lanes; intervals the scan does
+    not hold come back empty (the device reports them as a scan that ends early)."""
+    s, e = scan
+    if n_lanes == 1:
+        return [(s, e)]
+    a = np.frombuffer(d, np.uint8, e - s, s)
+    nxt = a[1:]
+    at = (np.flatnonzero((a[:-1] == 0xFF) & (nxt >= 0xD0) & (nxt <= 0xD7)) + s).tolist()[:n_lanes - 1]
+    begins = [s] + [x + 2 for x in at]
+    ends = at + [e]
+    out = list(zip(begins, ends))
+    return out + [(e, e)] * (n_lanes - len(out))
+
+
+def geometry(info):
+    """(ncomp, hs, vs, mcux, mcuy, blocks per component) of a parsed file."""
+    nc = len(info.components)
+    hs, vs = (info.components[0].h, info.components[0].v) if nc == 3 else (1, 1)
+    mcux, mcuy = -(-info.width // (8 * hs)), -(-info.height // (8 * vs))
+    blocks = [mcux * hs * mcuy * vs] + [mcux * mcuy] * (nc - 1)
+    return nc, hs, vs, mcux, mcuy, blocks
+
+
+def _align(x, a=16):
+    return (x + a - 1) // a * a
+
+
+def build_blob(datas, infos):
+    """Everything the device needs for one call, in one byte array: header | image table | lane table | Huffman table sets | quantisation
+    tables | the scans' bytes + SCAN_PAD zeros.  -> (blob uint8 array, header record, image table)."""
+    B = len(infos)
+    images = np.zeros(B, IMAGE_DT)
+    quant = np.zeros((B, 3, 64), np.uint16)
+    tabsets, set_bytes, groups = {}, [], []
+    coef = plane = outb = scanb = 0
+    scan_at = []
+    for i, (d, info) in enumerate(zip(datas, infos)):
+        nc, hs, vs, mcux, mcuy, blocks = geometry(info)
+        im = images[i]
+        im["coef_off"], im["plane_off"], im["out_off"] = coef, plane, outb
+        im["w"], im["h"], im["ncomp"], im["hs"], im["vs"], im["mcux"], im["mcuy"], im["quant"] = info.width, info.height, nc, hs, vs, mcux, mcuy, 3 * i
+        for c, comp in enumerate(info.components):
+            quant[i, c] = info.qtables[comp.tq]
+            im["dc_tab"][c], im["ac_tab"][c] = comp.td, comp.ta
+        coef += 64 * sum(blocks)
+        plane += 64 * sum(blocks)
+        outb += _align(3 * info.width * info.height)
+        key = tuple(None if k not in info.huffman else (info.huffman[k][0].tobytes(), info.huffman[k][1].tobytes())
+                    for k in ((0, 0), (0, 1), (1, 0), (1, 1)))
+        if key not in tabsets:
+            tabsets[key] = len(set_bytes)
+            set_bytes.append(np.concatenate([np.zeros(HUFF_TABLE_BYTES, np.uint8) if t is None else
+                                             huff_device_table(np.frombuffer(t[0], np.uint8), np.frombuffer(t[1], np.uint8)) for t in key]))
+            groups.append([])
+        ts = tabsets[key]
+        total = mcux * mcuy
+        ri = info.restart_interval if info.restart_interval else total
+        nl = -(-total // ri)
+        s, e = info.scan
+        for k, (b0, b1) in enumerate(_restart_ranges(d, info.scan, nl)):
+            groups[ts].append((scanb + b0 - s, scanb + b1 - s, i, k * ri, min(ri, total - k * ri), ts))
+        scan_at.append(scanb)
+        scanb += e - s
+    rows, group = [], 1
+    while group < MAX_GROUP and sum(len(g) for g in groups) > WAVE_SLOTS * group:
+        group *= 2
+    for ts, g in enumerate(groups):                          # lanes of one workgroup share a table set: pad every set's lanes to whole groups
+        rows += g + [(0, 0, -1, 0, 0, ts)] * (-len(g) % group)
+    lanes = np.array(rows, LANE_DT)
+    hdr = np.zeros(1, HEADER_DT)[0]
+    off = _align(HEADER_DT.itemsize)
+    hdr["n_images"], hdr["n_lanes"], hdr["n_tabsets"], hdr["group"] = B, len(lanes), len(set_bytes), group
+    hdr["images_off"] = off
+    off = _align(off + images.nbytes)
+    hdr["lanes_off"] = off
+    off = _align(off + lanes.nbytes)
+    hdr["huff_off"] = off
+    off = _align(off + HUFF_SET_BYTES * len(set_bytes))
+    hdr["quant_off"] = off
+    off = _align(off + quant.nbytes)
+    hdr["scan_off"] = off
+    hdr["scan_bytes"] = _align(scanb + SCAN_PAD)           # a multiple of 8: the bit reader loads aligned 8-byte words
+    hdr["total_bytes"] = off + _align(scanb + SCAN_PAD)
+    hdr["coef_elems"], hdr["plane_bytes"], hdr["out_bytes"] = coef, plane, outb
+    if hdr["total_bytes"] >= 2 ** 31 or B > 65535:
+        raise MafError("jpeg: decode() takes up to 65535 files and 2 GiB of file bytes per call")
+    return hdr, images, lanes, np.concatenate(set_bytes), quant, scan_at
+
+
+def fill_blob(buf, hdr, images, lanes, huff, quant, datas, infos, scan_at):
+    """Write the sections of build_blob into `buf` (a uint8 array of hdr.total_bytes: the pinned staging buffer)."""
+    buf[:HEADER_DT.itemsize] = np.frombuffer(hdr.tobytes(), np.uint8)
+    for name, arr in (("images_off", images), ("lanes_off", lanes), ("huff_off", huff), ("quant_off", quant)):
+        o = int(hdr[name])
+        buf[o:o + arr.nbytes] = arr.reshape(-1).view(np.uint8)
+    so = int(hdr["scan_off"])
+    for d, info, at in zip(datas, infos, scan_at):
+        s, e = info.scan
+        buf[so + at:so + at + e - s] = np.frombuffer(d, np.uint8, e - s, s)
+    buf[so + (scan_at[-1] + infos[-1].scan[1] - infos[-1].scan[0] if infos else 0):] = 0      # at least SCAN_PAD zero bytes
+
+
+_lib_checked = False
+
+
+def _library():
+    """The HIP library, with the struct sizes of this binding checked against it once."""
+    global _lib_checked
+    L = lib.load()
+    if not _lib_checked:
+        import ctypes
+        sizes = (ctypes.c_int32 * 3)()
+        lib.check(L.maf_jpeg_struct_sizes(sizes))
+        if list(sizes) != [HEADER_DT.itemsize, IMAGE_DT.itemsize, LANE_DT.itemsize]:
+            raise MafError("libmafyolo_hip.so was built for maf_jpeg_* structs of %s bytes, this binding declares %s: rebuild"
+                           % (list(sizes), [HEADER_DT.itemsize, IMAGE_DT.itemsize, LANE_DT.itemsize]))
+        _lib_checked = True
+    return L
+
+
+def _name(f, i):
+    return "file %d (%s)" % (i, os.fspath(f)) if isinstance(f, (str, os.PathLike)) else "file %d" % i
+
+
+def status_text(word):
+    return ", ".join(t for bit, t in _STATUS_TEXT if word & bit) or "status 0x%x" % word
+
+
+def decode(files, device=None, stream=None, ignore_orientation=False, check=True, stages=STAGE_ALL, taps=None):
+    """Decode a list of baseline JPEG files (bytes-like objects or paths; mixed sizes and samplings welcome) on the device.
+    -> a list of uint8 [h_i, w_i, 3] BGR CUDA tensors (views of one allocation), what cv2.imread returns for each file; they go into
+    letterbox / eval_batch / detect_frames / train_batch as they are.  With check=True (the default) the per-image status words are read
+    once after the launches (the call's one synchronisation) and a fault raises MafError naming the file; check=False returns
+    (frames, status int32 [B]) without synchronising.  `stream`: a torch.cuda.Stream to work on (default: the current one).
+    `taps`: a dict that receives the intermediate buffers (coefficients, planes, the image table) — tests and the probe."""
+    import torch
+    files = list(files)
+    if not files:
+        raise MafError("jpeg.decode: no files")
+    dev = torch.device("cuda" if device is None else device)
+    if dev.type != "cuda":
+        raise MafError("jpeg.decode runs on the HIP path only (no CPU fallback): device %s" % dev)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    datas, infos = [], []
+    for i, f in enumerate(files):
+        d = _bytes(f)
+        try:
+            info = parse(d)
+        except MafError as e:
+            raise type(e)("%s: %s" % (_name(f, i), e)) from None
+        if info.orientation not in (None, 1) and not ignore_orientation:
+            raise JpegUnsupported("%s: jpeg: EXIF orientation %d — cv2.imread would rotate the frame, this decoder does not "
+                                  "(pass ignore_orientation=True to take the stored pixels)" % (_name(f, i), info.orientation))
+        datas.append(d)
+        infos.append(info)
+    hdr, images, lanes, huff, quant, scan_at = build_blob(datas, infos)
+    L = _library()
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev), torch.cuda.stream(st):
+        stage = torch.empty(int(hdr["total_bytes"]), dtype=torch.uint8, pin_memory=True)
+        host = stage.numpy()
+        fill_blob(host, hdr, images, lanes, huff, quant, datas, infos, scan_at)
+        blob = stage.to(dev, non_blocking=True)                                  # the call's one host -> device copy
+        coef = torch.empty(int(hdr["coef_elems"]), dtype=torch.int16, device=dev)
+        planes = torch.empty(int(hdr["plane_bytes"]), dtype=torch.uint8, device=dev)
+        out = torch.empty(int(hdr["out_bytes"]), dtype=torch.uint8, device=dev)
+        status = torch.empty(len(files), dtype=torch.int32, device=dev)
+        lib.check(L.maf_jpeg_decode(host.ctypes.data, blob.data_ptr(), coef.data_ptr(), planes.data_ptr(), out.data_ptr(), status.data_ptr(),
+                                    int(stages), st.cuda_stream))
+        frames = []
+        for im in images:
+            o, h, w = int(im["out_off"]), int(im["h"]), int(im["w"])
+            frames.append(out[o:o + 3 * h * w].view(h, w, 3))
+        if taps is not None:
+            taps.update(coef=coef, planes=planes, images=images, status=status, header=hdr)
+        if not check:
+            return frames, status
+        words = status.tolist()                                                  # the one synchronisation (it also keeps `stage` alive until the copy is done)
+    bad = [(i, w) for i, w in enumerate(words) if w]
+    if bad:
+        raise MafError("jpeg.decode: " + "; ".join("%s: %s" % (_name(files[i], i), status_text(w)) for i, w in bad))
+    return frames

@@ -1,0 +1,105 @@
+"""Measurements of the JPEG decoder (csrc/jpeg_decode.hip, maf-yolo_amd/jpeg.py) on the GPU; prints ONE JSON line.
+
+    python tools/jpeg_probe.py [--iters N] [--batches 32,256,1024]
+
+The file is the 480 x 640, 4:2:0, quality 90 case of tests/golden/jpeg_cases.npz replicated to B files per call.  Per B:
+* images/s of decode(files, check=False) end to end (host parse + staging + copy + the three kernels), wall clock over `iters` calls with
+  one synchronisation at the end, and of decode(files) with its status read per call;
+* the host's share: wall time of a call with the device idle behind it (enqueue only);
+* per-stage device times from event pairs around maf_jpeg_decode restricted to one stage (entropy includes the coefficient memset);
+* bytes moved per call: file bytes copied host -> device, coefficients written + read, planes written + read, frame bytes written.
+Where Pillow is importable, the single-thread Pillow decode time of the same file stands beside them.
+"""
+import argparse
+import io
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from maf_yolo_amd import jpeg as J, lib  # noqa: E402
+
+DEV = torch.device("cuda:0")
+
+
+def stage_times(files, iters):
+    """Event time of each stage alone, on buffers a full decode has filled."""
+    infos = [J.parse(f) for f in files]
+    hdr, images, lanes, huff, quant, scan_at = J.build_blob(files, infos)
+    stage = torch.empty(int(hdr["total_bytes"]), dtype=torch.uint8, pin_memory=True)
+    host = stage.numpy()
+    J.fill_blob(host, hdr, images, lanes, huff, quant, files, infos, scan_at)
+    blob = stage.to(DEV)
+    coef = torch.empty(int(hdr["coef_elems"]), dtype=torch.int16, device=DEV)
+    planes = torch.empty(int(hdr["plane_bytes"]), dtype=torch.uint8, device=DEV)
+    out = torch.empty(int(hdr["out_bytes"]), dtype=torch.uint8, device=DEV)
+    status = torch.empty(len(files), dtype=torch.int32, device=DEV)
+    L = lib.load()
+    st = torch.cuda.current_stream(DEV)
+    res = {}
+    for name, mask in (("entropy", J.STAGE_ENTROPY), ("idct", J.STAGE_IDCT), ("color", J.STAGE_COLOR), ("all", J.STAGE_ALL)):
+        def run():
+            lib.check(L.maf_jpeg_decode(host.ctypes.data, blob.data_ptr(), coef.data_ptr(), planes.data_ptr(), out.data_ptr(), status.data_ptr(),
+                                        mask, st.cuda_stream))
+        run()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(iters):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); run(); e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1) * 1e3)
+        res[name + "_us"] = round(statistics.median(ts), 1)
+    res["bytes"] = dict(h2d=int(hdr["total_bytes"]), coef_write_read=4 * int(hdr["coef_elems"]), planes_write_read=2 * int(hdr["plane_bytes"]),
+                        frames=int(hdr["out_bytes"]), lanes=int((lanes["image"] >= 0).sum()))
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--batches", default="32,256,1024")
+    args = ap.parse_args()
+    z = np.load(os.path.join(ROOT, "tests", "golden", "jpeg_cases.npz"))
+    data = z["large_file"].tobytes()
+    res = {"metric": "jpeg_probe", "file": "480x640 4:2:0 q90, %d bytes" % len(data), "cases": {}}
+    try:
+        from PIL import Image
+        ts = []
+        for _ in range(20):
+            t0 = time.perf_counter()
+            np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
+            ts.append(time.perf_counter() - t0)
+        res["pillow_single_thread_ms"] = round(statistics.median(ts) * 1e3, 3)
+    except ImportError:
+        res["pillow_single_thread_ms"] = None
+    for B in [int(b) for b in args.batches.split(",")]:
+        files = [data] * B
+        J.decode(files, device=DEV)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.iters):
+            J.decode(files, device=DEV, check=False)
+        t_enq = time.perf_counter() - t0
+        torch.cuda.synchronize()
+        t_async = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        for _ in range(args.iters):
+            J.decode(files, device=DEV)
+        t_sync = time.perf_counter() - t0
+        c = dict(B=B, img_s_check_false=round(B * args.iters / t_async, 1), img_s_check_true=round(B * args.iters / t_sync, 1),
+                 host_enqueue_ms_per_call=round(t_enq / args.iters * 1e3, 2))
+        c.update(stage_times(files, max(3, args.iters)))
+        res["cases"][str(B)] = c
+        torch.cuda.empty_cache()
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
