@@ -49,6 +49,20 @@ enum { MAF_OP_STEM = 0,                  /* RepVGGBlock L0 deploy form: 3x3 s2 c
        MAF_OP_HEADTAIL = 8,              /* one detection level: {cls,reg}_conv_s -> {cls,reg}_pred -> sigmoid / DFL decode into the prediction rows */
        MAF_OP_STEM2 = 9,                 /* backbone.0 + backbone.1: image -> 1/4-resolution map, the 1/2-resolution tensor stays in LDS */
        MAF_OP_CONV3X3S2_DGRAD = 10 };    /* training: data gradient of a 3x3 stride-2 pad-1 conv (gather form, no atomics)              */
+/* maf_op_t.tile_k of MAF_OP_CONV1X1 / MAF_OP_CONV3X3S2: the kernel variant (described with the kinds below; 0 = MAF_CONV_GENERIC in the forward dispatch) */
+enum { MAF_CONV_GENERIC = 1,             /* each wave reduces all of K                                   */
+       MAF_CONV_LDS = 2,                 /* the workgroup shares each k-step's weight fragments through LDS */
+       MAF_CONV_STREAM = 3,              /* persistent waves, cross-tile prefetch (1x1, one direct source) */
+       MAF_CONV_SPLITK = 4,              /* the 4 waves of a workgroup split K (tile_p = 1)              */
+       MAF_CONV_STREAM_LDS = 5,          /* persistent waves, the channel tile's weights resident in LDS (1x1) */
+       MAF_CONV3_LDS = 6,                /* 3x3 s2: all weights and the input patch in LDS               */
+       MAF_CONV3_WREG = 7,               /* 3x3 s2: all weights in registers, patches by DMA             */
+       MAF_CONV_DMA = 8 };               /* MAF_CONV_LDS with the fragments arriving by DMA              */
+/* maf_op_t.tile_p < 0 of MAF_OP_DWCONV: the kernel (-3 left the library); their tile_k = tile rows * 256 + channels per block (DOT2) or waves per
+ * workgroup (PAIRS), the latter + MAF_DW_P2_STAGED for staged stores */
+enum { MAF_DW_MFMA = -1, MAF_DW_DOT2 = -2, MAF_DW_PAIRS = -4 };
+enum { MAF_DW_P2_STAGED = 128 };
+#define MAF_DW_TILE_ROWS(tile_k) ((tile_k) >> 8)
 enum { MAF_E_ARG = -1, MAF_E_UNSUPPORTED = -2, MAF_E_HIP = -3 };
 
 typedef struct {
@@ -159,7 +173,7 @@ typedef struct {
     int32_t out_stride, out_coff;
     int32_t out_f32;             /* CONV1X1: store fp32 regardless of dtype (cls_pred/reg_pred) */
     int32_t tile_p, tile_c;      /* MFMA tile: 16*tile_p pixels x 16*tile_c channels per wave   */
-    int32_t tile_k;              /* 0/1: each wave reduces all of K; 4: the 4 waves of a workgroup split K (tile_p = 1); 2 / 8: weight fragments shared through LDS */
+    int32_t tile_k;              /* convs: MAF_CONV_* / MAF_CONV3_* (0 = MAF_CONV_GENERIC; the dgrad op takes 0 / 1 only); other kinds: see above */
     const void* w;
     const float* bias;
     /* DECODE only */

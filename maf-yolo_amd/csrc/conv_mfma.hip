@@ -3,9 +3,9 @@
 #include "conv_mfma.inc.h"
 
 int maf_launch_conv_mfma(const maf_op_t* op, hipStream_t s) {
-    if (op->kind == MAF_OP_CONV3X3S2 && op->nc && op->tile_k != 6 && op->tile_k != 7) { maf_set_error("conv3x3s2: the pooled 1x1 branch (nc) exists in the tile_k = 6 and 7 kernels only"); return MAF_E_UNSUPPORTED; }
-    if (op->kind == MAF_OP_CONV3X3S2 && op->tile_k == 6) return maf_launch_conv3s2_lds(op, s);   // narrow layers: weights + input patch in LDS (conv3s2_lds.hip)
-    if (op->kind == MAF_OP_CONV3X3S2 && op->tile_k == 7) return maf_launch_conv3s2_wreg(op, s);  // 96 / 128 channels: weights in registers, patch by DMA (conv3s2_wreg.hip)
+    if (op->kind == MAF_OP_CONV3X3S2 && op->nc && op->tile_k != MAF_CONV3_LDS && op->tile_k != MAF_CONV3_WREG) { maf_set_error("conv3x3s2: the pooled 1x1 branch (nc) exists in the tile_k = 6 and 7 kernels only"); return MAF_E_UNSUPPORTED; }
+    if (op->kind == MAF_OP_CONV3X3S2 && op->tile_k == MAF_CONV3_LDS) return maf_launch_conv3s2_lds(op, s);   // narrow layers: weights + input patch in LDS (conv3s2_lds.hip)
+    if (op->kind == MAF_OP_CONV3X3S2 && op->tile_k == MAF_CONV3_WREG) return maf_launch_conv3s2_wreg(op, s);  // 96 / 128 channels: weights in registers, patch by DMA (conv3s2_wreg.hip)
     MAF_REQUIRE(op->dtype == MAF_F16 || op->dtype == MAF_F32, "conv: dtype must be f16/f32");
     const int CH = op->dtype == MAF_F16 ? 8 : 4, KS = op->dtype == MAF_F16 ? 32 : 16;
     MAF_REQUIRE(op->nsrc >= 1 && op->nsrc <= 4, "conv: nsrc must be 1..4");
@@ -45,16 +45,16 @@ int maf_launch_conv_mfma(const maf_op_t* op, hipStream_t s) {
     if (a.twin) {
         MAF_REQUIRE(op->aux[1] && op->aux[2] && op->aux[3], "conv twin: aux = {src, w, bias, out} of the second conv, all four");
         MAF_REQUIRE(op->nsrc == 1 && op->src[0].mode != MAF_SRC_UP2, "conv twin: single-source variants only");
-        MAF_REQUIRE(op->tile_k <= 2 || op->tile_k == 4 || op->tile_k == 8, "conv twin: generic, LDS-shared-weight and split-K variants only");
+        MAF_REQUIRE(op->tile_k <= MAF_CONV_LDS || op->tile_k == MAF_CONV_SPLITK || op->tile_k == MAF_CONV_DMA, "conv twin: generic, LDS-shared-weight and split-K variants only");
         a.src_t = op->aux[0]; a.w_t = op->aux[1]; a.bias_t = static_cast<const float*>(op->aux[2]); a.out_t = const_cast<void*>(op->aux[3]);
     }
     int pt = op->tile_p;
     const int ct = op->tile_c;
     MAF_REQUIRE(pt > 0 && ct > 0, "conv: tile_p/tile_c not set");
-    const bool ks4 = op->tile_k == 4;
-    MAF_REQUIRE((op->tile_k >= 0 && op->tile_k <= 5) || op->tile_k == 8, "conv: tile_k must be 1, 2 / 8 (weights through LDS), 3 / 5 (persistent streaming 1x1) or 4 (split-K)");
-    const bool stream = op->tile_k == 3;
-    const bool lb = op->tile_k == 2, dma = op->tile_k == 8;
+    const bool ks4 = op->tile_k == MAF_CONV_SPLITK;
+    MAF_REQUIRE((op->tile_k >= 0 && op->tile_k <= MAF_CONV_STREAM_LDS) || op->tile_k == MAF_CONV_DMA, "conv: tile_k must be 1, 2 / 8 (weights through LDS), 3 / 5 (persistent streaming 1x1) or 4 (split-K)");
+    const bool stream = op->tile_k == MAF_CONV_STREAM;
+    const bool lb = op->tile_k == MAF_CONV_LDS, dma = op->tile_k == MAF_CONV_DMA;
     MAF_REQUIRE(!(lb || dma) || (op->dtype == MAF_F16 && !op->out_f32), "conv: tile_k = 2 / 8 are fp16-output variants");
     MAF_REQUIRE(!ks4 || pt == 1, "conv: split-K (tile_k = 4) needs tile_p = 1");
     a.nM = ks4 ? maf_cdiv(a.M, 16) : maf_cdiv(a.M, 64 * pt);
@@ -64,7 +64,7 @@ int maf_launch_conv_mfma(const maf_op_t* op, hipStream_t s) {
     if (op->kind == MAF_OP_CONV3X3S2_DGRAD) {
         MAF_REQUIRE(op->nsrc == 1 && op->src[0].mode == MAF_SRC_DIRECT && !a.twin, "conv3x3s2 dgrad: single direct source (dY)");
         MAF_REQUIRE(op->Hin > 0 && op->Win > 0 && (op->H - 1) / 2 + 1 == op->Hin && (op->W - 1) / 2 + 1 == op->Win, "conv3x3s2 dgrad: Hin,Win (the dY grid) must equal floor((H-1)/2)+1");
-        MAF_REQUIRE(op->tile_k <= 1 && !op->out_f32 && op->act == MAF_ACT_NONE, "conv3x3s2 dgrad: generic variant, no epilogue");
+        MAF_REQUIRE(op->tile_k <= MAF_CONV_GENERIC && !op->out_f32 && op->act == MAF_ACT_NONE, "conv3x3s2 dgrad: generic variant, no epilogue");
         a.act = MAF_ACT_NONE;
         static const bool unsplit = getenv("MAF_DGRAD3_ALL_TAPS") != nullptr;          // A/B: every pixel walks all nine taps
         if (op->H % 2 == 0 && op->W % 2 == 0 && !unsplit) {                 // parity classes of equal size: each runs only its own taps
@@ -91,13 +91,13 @@ int maf_launch_conv_mfma(const maf_op_t* op, hipStream_t s) {
     a.act = op->act;
     MAF_REQUIRE(op->act >= 0 && op->act <= 3, "conv: bad act");
     a.out_pairs = op->out_pairs;
-    MAF_REQUIRE(!op->out_pairs || (op->kind == MAF_OP_CONV1X1 && op->tile_k == 5 && !a.twin && a.M % 2 == 0 && op->W % 2 == 0 && op->out_coff % 4 == 0 && op->out_stride % 4 == 0),
+    MAF_REQUIRE(!op->out_pairs || (op->kind == MAF_OP_CONV1X1 && op->tile_k == MAF_CONV_STREAM_LDS && !a.twin && a.M % 2 == 0 && op->W % 2 == 0 && op->out_coff % 4 == 0 && op->out_stride % 4 == 0),
                 "conv: out_pairs (pixel-pair output) is a tile_k = 5 conv1x1 option: even width, out_coff and out_stride multiples of 4");
     if (stream) {
         MAF_REQUIRE(op->dtype == MAF_F16 && !op->out_f32 && var == VAR_DIRECT && a.nsrc == 1, "conv: tile_k = 3 is an fp16 single-direct-source 1x1 variant");
         return maf_conv1x1_stream(a, pt, ct, s);
     }
-    if (op->tile_k == 5) {
+    if (op->tile_k == MAF_CONV_STREAM_LDS) {
         MAF_REQUIRE(op->dtype == MAF_F16 && !op->out_f32 && (pt == 1 || pt == 2) && (var == VAR_DIRECT || var == VAR_MULTI || (var == VAR_POOL2 && op->kind == MAF_OP_CONV1X1)),
                     "conv: tile_k = 5 is an fp16 1x1 variant with tile_p = 1 (4 waves per workgroup) or 2 (8 waves)");
         a.nM = maf_cdiv(a.M, 16);

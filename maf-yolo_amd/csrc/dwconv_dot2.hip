@@ -260,7 +260,7 @@ int maf_launch_dwconv_dot2(const maf_op_t* op, hipStream_t s) {
     a.in = static_cast<const half_t*>(sr.ptr); a.w = static_cast<const half_t*>(op->w); a.bias = op->bias; a.out = static_cast<half_t*>(op->out);
     a.B = op->B; a.H = op->H; a.W = op->W; a.C = op->Cout; a.in_mod = op->Cin;
     a.in_stride = sr.stride; a.in_coff = sr.coff; a.out_stride = op->out_stride; a.out_coff = op->out_coff;
-    a.TW = op->tile_c; a.TH = op->tile_k >> 8; a.CB = op->tile_k & 255;
+    a.TW = op->tile_c; a.TH = MAF_DW_TILE_ROWS(op->tile_k); a.CB = op->tile_k & 255;
     const int k = op->ksize;
     MAF_REQUIRE(k == 3 || k == 5 || k == 7 || k == 9, "dwconv: k must be 3, 5, 7 or 9");
     MAF_REQUIRE(a.TW > 0 && a.TW % 8 == 0 && a.TH > 0 && a.CB > 0 && a.CB % 8 == 0 && a.CB <= 64, "dwconv (dot2): tile_c = columns (multiple of 8), tile_k = rows * 256 + channels (multiple of 8, <= 64)");

@@ -290,9 +290,9 @@ int maf_launch_dwconv_p2(const maf_op_t* op, hipStream_t s) {
     a.in = static_cast<const half_t*>(sr.ptr); a.w = static_cast<const uint32_t*>(op->aux[1]); a.bias = op->bias; a.out = static_cast<half_t*>(op->out);
     a.B = op->B; a.H = op->H; a.W = op->W; a.C = op->Cout; a.in_groups = op->Cin / 8; a.nf = op->Cout / op->Cin;
     a.in_stride = sr.stride; a.in_coff = sr.coff; a.out_stride = op->out_stride; a.out_coff = op->out_coff;
-    a.TW = op->tile_c; a.TH = op->tile_k >> 8;
-    const int nw = op->tile_k & 127;
-    const bool stage = (op->tile_k & 128) != 0;
+    a.TW = op->tile_c; a.TH = MAF_DW_TILE_ROWS(op->tile_k);
+    const int nw = op->tile_k & (MAF_DW_P2_STAGED - 1);
+    const bool stage = (op->tile_k & MAF_DW_P2_STAGED) != 0;
     MAF_REQUIRE(a.TW > 0 && a.TW % R == 0 && a.TH > 0 && nw >= 1 && nw <= 8, "dwconv (pairs): tile_c = columns (multiple of 4), tile_k = rows * 256 + waves per workgroup (1..8) [+ 128]");
     a.SPR = a.TW / R;
     a.PITCH = p2_pitch(a.TH, a.TW, k);

@@ -20,7 +20,8 @@ from .layers import (RepVGGBlock, RepHDW, MPRep, SPPF, ConvWrapper, Head_DepthUn
 _ESIZE = {lib.F16: 2, lib.F32: 4}
 
 
-from .tuner import _TUNE_CACHE, choose_fusion, stream_lds_ok, save_tune_cache, load_tune_cache, p2_wave_bytes      # noqa: F401  (measured choices: tuner.py)
+from .conv_variants import stream_lds_ok      # noqa: F401  (re-exported)
+from .tuner import _TUNE_CACHE, choose_fusion, save_tune_cache, load_tune_cache, p2_wave_bytes      # noqa: F401  (measured choices: tuner.py)
 from . import tuner as _tuner, plan_report as _report
 
 _TORCH_DT = {lib.F16: torch.float16, lib.F32: torch.float32}
@@ -330,7 +331,7 @@ class Plan:
                     # ... and on the register-resident 3x3 kernel (csrc/conv3s2_wreg.hip with nc): the pooled operand is the maximum of four fragments the conv reads anyway
                     w2_, b2_ = m.conv2.fused()
                     self._ops.append(dict(kind=lib.OP_CONV3X3S2, name=p + ".conv1+conv2", act=lib.ACT_RELU, H=x.H // 2, W=x.W // 2, Hin=x.H, Win=x.W, Cin=x.C, Cout=c_,
-                                          raw=(w2_.detach().float().cpu(), b2_.detach().float().cpu(), None), pool1=(w1_.detach().float().cpu(), b1_.detach().float().cpu()), pool1_tk=7,
+                                          raw=(w2_.detach().float().cpu(), b2_.detach().float().cpu(), None), pool1=(w1_.detach().float().cpu(), b1_.detach().float().cpu()), pool1_tk=lib.CONV3_WREG,
                                           segs=x.segs, out=out, out_coff=c_, out_f32=0, pt=2, ct=8, w=self._wput(pack.pack_mprep_wreg(w2_, b2_, w1_, b1_)), b=0))
                     y.append(TV([Seg(out, node.cout)], out.H, out.W))
                     continue
@@ -529,7 +530,7 @@ class Plan:
                 o.out_stride = r["out"].stride
             o.out_coff = r["out_coff"]
             o.out_f32 = r.get("out_f32", 0)
-            o.tile_p, o.tile_c, o.tile_k = r.get("pt", 0), r.get("ct", 0), (1 if r["kind"] in (lib.OP_CONV1X1, lib.OP_CONV3X3S2) else 0)
+            o.tile_p, o.tile_c, o.tile_k = r.get("pt", 0), r.get("ct", 0), (lib.CONV_GENERIC if r["kind"] in (lib.OP_CONV1X1, lib.OP_CONV3X3S2) else 0)
             o.ksize = r.get("ksize", 0)
             if "w" in r:
                 o.w = wbase + r["w"]
@@ -538,7 +539,7 @@ class Plan:
                 o.tile_k = r["tk"]
                 o.nc = r.get("tail_c3", 0)
             if "pool1" in r:                                  # one-launch MPRep: only the LDS-resident 3x3 kernel has the pooled branch
-                o.tile_k, o.nc, o.reg_stride = r.get("pool1_tk", 6), r["pool1"][0].shape[0], 0
+                o.tile_k, o.nc, o.reg_stride = r.get("pool1_tk", lib.CONV3_LDS), r["pool1"][0].shape[0], 0
             for k_, off in enumerate(r.get("aux", [])):
                 if off is not None:
                     o.aux[k_] = wbase + off
@@ -583,7 +584,7 @@ class Plan:
         if i == 0 or self.dtype != lib.F16 or o.kind != lib.OP_DWCONV or not o.aux[1] or o.W % 2 or o.Cin % 8 or o.nsrc != 1 or o.src[0].mode not in (lib.SRC_DIRECT, lib.SRC_PAIRS):
             return None
         p = self.ops[i - 1]
-        if p.kind != lib.OP_CONV1X1 or p.tile_k != 5 or p.out_f32 or "twin" in self._ops[i - 1] or p.out != o.src[0].ptr or p.out_coff or o.src[0].coff \
+        if p.kind != lib.OP_CONV1X1 or p.tile_k != lib.CONV_STREAM_LDS or p.out_f32 or "twin" in self._ops[i - 1] or p.out != o.src[0].ptr or p.out_coff or o.src[0].coff \
                 or p.Cout != o.Cin or p.out_stride != o.src[0].stride or p.out_stride % 4 or (p.B, p.H, p.W) != (o.B, o.H, o.W):
             return None
         for j, q in enumerate(self.ops):                                    # any other reader (or writer) of the buffer keeps it NHWC

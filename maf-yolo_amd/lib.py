@@ -18,6 +18,22 @@ NMS_SINGLE_LAUNCH = 2         # maf_nms_ex flag: one launch (collect, then the l
 ACT_NONE, ACT_RELU, ACT_SILU, ACT_SIGMOID = 0, 1, 2, 3
 SRC_DIRECT, SRC_UP2, SRC_POOL2, SRC_SUB2, SRC_PAIRS = 0, 1, 2, 3, 4
 OP_STEM, OP_CONV1X1, OP_CONV3X3S2, OP_DWCONV, OP_SPPF_POOL, OP_DECODE, OP_BOTTLENECK, OP_CONV1DW, OP_HEADTAIL, OP_STEM2, OP_CONV3X3S2_DGRAD = range(11)
+# MAF_CONV_* / MAF_CONV3_*: the kernel variant a conv op's tile_k selects (0 = CONV_GENERIC in the forward dispatch)
+CONV_GENERIC, CONV_LDS, CONV_STREAM, CONV_SPLITK, CONV_STREAM_LDS, CONV3_LDS, CONV3_WREG, CONV_DMA = range(1, 9)
+CONV_VARIANT_NAMES = {CONV_GENERIC: "generic", CONV_LDS: "lds", CONV_STREAM: "stream", CONV_SPLITK: "k4", CONV_STREAM_LDS: "streamlds", CONV3_LDS: "ldsall",
+                      CONV3_WREG: "wreg", CONV_DMA: "dma"}
+DW_MFMA, DW_DOT2, DW_PAIRS = -1, -2, -4       # MAF_DW_*: the kernel a depth-wise op's negative tile_p selects
+DW_P2_STAGED = 128                            # MAF_DW_P2_STAGED: staged stores of the DW_PAIRS kernel, a bit of its tile_k
+
+
+def dw_tile_k(rows, low, staged=False):
+    """tile_k of a DW_DOT2 (low = channels per block) or DW_PAIRS (low = waves per workgroup) launch with `rows` tile rows."""
+    return rows * 256 + low + (DW_P2_STAGED if staged else 0)
+
+
+def dw_tile_k_split(tile_k):
+    """(rows, low, staged) of such a tile_k."""
+    return tile_k >> 8, tile_k & (DW_P2_STAGED - 1), bool(tile_k & DW_P2_STAGED)
 
 
 class MafSrc(C.Structure):

@@ -329,7 +329,7 @@ def pack_stem2(w0, b0, w1, b1, w3=None, b3=None):
 
 
 def pack_conv3x3_lds(w, b):
-    """Record of the LDS-resident 3x3 stride-2 conv (csrc/conv3s2_lds.hip, tile_k = 6): w [Cout, Cin, 3, 3], b [Cout] -> fragments
+    """Record of the LDS-resident 3x3 stride-2 conv (csrc/conv3s2_lds.hip, tile_k = lib.CONV3_LDS): w [Cout, Cin, 3, 3], b [Cout] -> fragments
     [ceil(9*Cin/8 / 4)][Cout/16][64 lanes][8] f16 (lane (g, n) of k-step s: pair q = 4s + g -> tap q // (Cin/8), channel group q % (Cin/8);
     element j = input channel 8*group + j; output channel 16t + n; zero for pairs past the last tap) | bias fp32 [Cout]."""
     w = w.detach().float().cpu()
@@ -349,7 +349,7 @@ def pack_conv3x3_lds(w, b):
 
 
 def pack_mprep_lds(w, b, w1, b1):
-    """Record of MPRep in one launch (csrc/conv3s2_lds.hip, tile_k = 6 with nc = C1: cat(conv1(MaxPool2d(2, 2)(x)), conv2(x)), common.py:776-792):
+    """Record of MPRep in one launch (csrc/conv3s2_lds.hip, tile_k = lib.CONV3_LDS with nc = C1: cat(conv1(MaxPool2d(2, 2)(x)), conv2(x)), common.py:776-792):
     pack_conv3x3_lds(w, b) of conv2, then conv1 — w1 [C1, Cin, 1, 1], b1 [C1] — as fragments [ceil(Cin / 32)][C1 / 16][64 lanes][8] f16 (lane (g, n)
     of k-step s: output channel 16t + n, input channels 32s + 8g .. + 7, zero past Cin) | bias fp32 [C1]."""
     w1 = w1.detach().float().cpu().reshape(w1.shape[0], -1)
@@ -367,12 +367,12 @@ _WREG_SHAPES = {(128, 128): (8, 1), (96, 96): (6, 1), (96, 64): (4, 2), (64, 64)
 
 
 def conv3x3_wreg_shape(cin, cout):
-    """(waves along the channels, waves along the pixels) of the register-resident 3x3 stride-2 conv (csrc/conv3s2_wreg.hip, tile_k = 7), or None."""
+    """(waves along the channels, waves along the pixels) of the register-resident 3x3 stride-2 conv (csrc/conv3s2_wreg.hip, tile_k = lib.CONV3_WREG), or None."""
     return _WREG_SHAPES.get((cin, cout))
 
 
 def pack_mprep_wreg(w, b, w1, b1):
-    """Record of MPRep in one launch on the register-resident 3x3 kernel (csrc/conv3s2_wreg.hip, tile_k = 7 with nc = C1; 96 -> 96 + 96): pack_conv3x3_wreg(w, b)
+    """Record of MPRep in one launch on the register-resident 3x3 kernel (csrc/conv3s2_wreg.hip, tile_k = lib.CONV3_WREG with nc = C1; 96 -> 96 + 96): pack_conv3x3_wreg(w, b)
     of conv2, then conv1 — w1 [C1, Cin, 1, 1], b1 [C1] — as fragments [C1 / 16 channel tiles][Cin / 32 k-steps][64 lanes][8] f16 (lane (g, n) of k-step j of
     tile t: output channel 16t + n, input channels 32j + 8g .. + 7) | bias fp32 [C1]."""
     w1 = w1.detach().float().cpu().reshape(w1.shape[0], -1)
@@ -383,7 +383,7 @@ def pack_mprep_wreg(w, b, w1, b1):
 
 
 def pack_conv3x3_wreg(w, b):
-    """Record of the register-resident-weight 3x3 stride-2 conv (csrc/conv3s2_wreg.hip, tile_k = 7): w [Cout, Cin, 3, 3], b [Cout] -> fragments
+    """Record of the register-resident-weight 3x3 stride-2 conv (csrc/conv3s2_wreg.hip, tile_k = lib.CONV3_WREG): w [Cout, Cin, 3, 3], b [Cout] -> fragments
     [Cout / 16 channel tiles][9 * Cin / 32 k-steps][64 lanes][8] f16 — lane (g, n) of k-step s of tile t: output channel 16 t + n, pair q = 4 s + g ->
     tap q // (Cin / 8) (tap-major: uniform per k-step since Cin % 32 == 0), channel group q % (Cin / 8), element j = input channel 8 * group + j —
     followed by the bias, fp32 [Cout]."""

@@ -20,23 +20,23 @@ def kernel_name(plan, idx):
         else:
             var = 1
         outf32 = "true" if (o.out_f32 and o.dtype == lib.F16) else "false"
-        if o.tile_k == 3:
+        if o.tile_k == lib.CONV_STREAM:
             return "conv1x1_stream_kernel<%d, %d, %d>" % (o.tile_p, o.tile_c, -(-o.Cin // 32))
-        if o.tile_k == 6:
+        if o.tile_k == lib.CONV3_LDS:
             return "conv3s2_lds_kernel<%d, %d, 4, %d>" % (o.Cin, o.Cout, o.nc)
-        if o.tile_k == 7:
+        if o.tile_k == lib.CONV3_WREG:
             return "conv3s2_wreg_kernel<%d, %d, %d, %d, %d, %d>" % ((o.Cin, o.Cout) + pack.conv3x3_wreg_shape(o.Cin, o.Cout) + (2 if o.tile_p == 2 else 3, o.nc))
-        if o.tile_k == 5:
+        if o.tile_k == lib.CONV_STREAM_LDS:
             return "conv1x1_stream_lds_kernel<%d, %d, %s, %d, false>" % (o.tile_c, sum(-(-o.src[k].C // 32) for k in range(o.nsrc)), "true" if var == 1 else "false", 8 if o.tile_p == 2 else 4)      # (last: the statistics epilogue of the training form — never in a plan)
-        return "conv_mfma_kernel<%s, %d, %d, %d, %s, %s, %s, %s>" % (T, o.tile_p, o.tile_c, var, outf32, "true" if o.tile_k == 4 else "false", "true" if o.tile_k in (2, 8) else "false",
-                                                                     "true" if o.tile_k == 8 else "false")
+        return "conv_mfma_kernel<%s, %d, %d, %d, %s, %s, %s, %s>" % (T, o.tile_p, o.tile_c, var, outf32, "true" if o.tile_k == lib.CONV_SPLITK else "false", "true" if o.tile_k in (lib.CONV_LDS, lib.CONV_DMA) else "false",
+                                                                     "true" if o.tile_k == lib.CONV_DMA else "false")
     if o.kind == lib.OP_DWCONV:
-        if o.tile_p == -1:
+        if o.tile_p == lib.DW_MFMA:
             return "dwconv_mfma_kernel<%d, %d>" % (o.ksize, o.act)
-        if o.tile_p == -4:
-            return "dwconv_p2_kernel<%d, %d, %d>" % (o.ksize, o.act, (o.Cout // o.Cin) if o.tile_k & 128 else 0)
-        if o.tile_p == -2:
-            return "dwconv_dot2_kernel<%d, 8, %d, %d>" % (o.ksize, 2 if (o.tile_k >> 8) % 2 == 0 else 1, o.act)
+        if o.tile_p == lib.DW_PAIRS:
+            return "dwconv_p2_kernel<%d, %d, %d>" % (o.ksize, o.act, (o.Cout // o.Cin) if lib.dw_tile_k_split(o.tile_k)[2] else 0)
+        if o.tile_p == lib.DW_DOT2:
+            return "dwconv_dot2_kernel<%d, 8, %d, %d>" % (o.ksize, 2 if lib.dw_tile_k_split(o.tile_k)[0] % 2 == 0 else 1, o.act)
         return "dwconv_tile_kernel<%s, %d, %d>" % (T, o.ksize, o.act)
     if o.kind == lib.OP_BOTTLENECK:
         return "bottleneck_kernel<%d, %d, %d, %d, %d>" % (o.ksize, -(-o.Cin // 32), 2 if o.Cout <= 32 else 4, o.nc // 16, o.nsrc if o.nc else 0)

@@ -10,7 +10,7 @@ import ctypes as C
 import torch
 import torch.nn.functional as F
 
-from . import lib, pack
+from . import conv_variants, lib, pack
 from . import train_ops as T
 
 
@@ -198,69 +198,33 @@ def _conv3_choice(op, key, cands, w, transpose, dt, dev):
     if best is not None:
         return best
     torch.cuda.synchronize(dev)
-    timer, st, res = lib.Timer(), T._stream(dev), []
+    st, ops, packs = T._stream(dev), [], {}
     saved, T.profile = T.profile, None
     saved_plan, T._plan = T._plan, None                                             # the candidates' weight forms are packed here and now: only the winner's joins the staging plan
     L = lib._lib if lib._lib is not None else lib.load()                        # (never through a recording tape's proxy)
+
+    def launch(o):
+        if L.maf_op_launch(C.byref(o), st) != 0:
+            raise lib.MafError(L.maf_last_error().decode())
+
     try:
         for pt, ct, tk in cands:
-            n = op.Cout
-            op.tile_p, op.tile_c, op.tile_k = pt, ct, tk
-            op.w, op.bias = T._packed_3x3(w, transpose, dt, ct, dev).data_ptr(), T._zero_bias(dev, -(-n // (16 * ct)) * 16 * ct).data_ptr()
-            if L.maf_op_launch(C.byref(op), st) != 0:
-                continue
-            ts = []
-            for _ in range(3):
-                timer.start(st)
-                L.maf_op_launch(C.byref(op), st)
-                timer.stop(st)
-                ts.append(timer.elapsed_ms())
-            res.append((min(ts), pt, ct, tk))
+            if ct not in packs:
+                packs[ct] = T._packed_3x3(w, transpose, dt, ct, dev), T._zero_bias(dev, -(-op.Cout // (16 * ct)) * 16 * ct)
+            o = lib.MafOp.from_buffer_copy(op)
+            o.tile_p, o.tile_c, o.tile_k, o.w, o.bias = pt, ct, tk, packs[ct][0].data_ptr(), packs[ct][1].data_ptr()
+            ops.append(o)
+        res = sorted((t, o.tile_p, o.tile_c, o.tile_k) for t, o in conv_variants.time_candidates(launch, ops, st, 3, "skip"))
     finally:
         T.profile, T._plan = saved, saved_plan
-    res.sort()
     best = T._conv3_tune[key] = res[0][1:] if res else cands[-1]
     T.stats["conv_tuned"] = T.stats.get("conv_tuned", 0) + 1
     return best
 
 
 def _conv3_fwd_cands(cin, cout, M, static):
-    cands = []
-    ksteps = 9 * -(-cin // 32)
-    for ct in (2, 4, 6, 8):
-        nt = -(-cout // (16 * ct))
-        if nt * 16 * ct > 2 * max(cout, 32) or (ct == 8 and cout % 8):
-            continue
-        for pt in (1, 2, 4):
-            if (pt == 4 and ct > 4) or (pt > 1 and -(-M // (64 * pt)) * nt < 256):
-                continue
-            cands.append((pt, ct, 1))
-        if M <= 65536:
-            cands.append((1, ct, 4))                                             # split-K across the four waves
-        if ct >= 4:
-            for pt in ((1, 2, 4) if ct == 4 else (1, 2)):                        # each k-step's weight fragments through LDS once per workgroup
-                if pt == 1 or -(-M // (64 * pt)) * nt >= 256:
-                    cands.append((pt, ct, 2))
-                    if pt <= 2:
-                        cands.append((pt, ct, 8))                                # ... by DMA, two k-steps per barrier (csrc/conv_mfma_dma.hip)
-    if static not in cands:
-        cands.append(static)
-    return cands
-
-
-def _conv3_dgrad_cands(cin, M, static):
-    cands = []
-    for ct in (2, 4, 8):
-        nt = -(-cin // (16 * ct))
-        if nt * 16 * ct > 2 * max(cin, 32):
-            continue
-        for pt in (1, 2, 4):
-            if (pt == 4 and ct > 4) or (pt > 1 and -(-M // (128 * pt)) * nt < 256):
-                continue
-            cands.append((pt, ct, 0))
-    if static not in cands:
-        cands.append(static)
-    return cands
+    # (no CONV3_LDS / CONV3_WREG: their records hold a bias, the training conv has none)
+    return conv_variants.with_static(conv_variants.conv_tiles(lib.OP_CONV3X3S2, lib.F16, M, [(cin, lib.SRC_DIRECT)], cout, cout, fused_3x3=False), static)
 
 
 @T._laned
@@ -276,7 +240,7 @@ class _Conv3x3s2(torch.autograd.Function):
         Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         dt = T._DT[x.dtype]
         pt, ct = pack.tile_for(cout, B * Ho * Wo)
-        tk = 1
+        tk = lib.CONV_GENERIC
         out = T._empty((B, cout, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
         op = lib.MafOp()
         op.kind, op.dtype, op.in_dtype, op.act = lib.OP_CONV3X3S2, dt, dt, lib.ACT_NONE
@@ -287,7 +251,7 @@ class _Conv3x3s2(torch.autograd.Function):
             key = ("f", B * Ho * Wo, cin, cout, xs)
             ch = T._conv3_tune.get(key)
             if ch is None and T._rec is None:                                      # (never timed inside a recording step: the static tile then)
-                ch = T._conv3_choice(op, key, T._conv3_fwd_cands(cin, cout, B * Ho * Wo, (pt, ct, 1)), w, False, dt, x.device)
+                ch = T._conv3_choice(op, key, T._conv3_fwd_cands(cin, cout, B * Ho * Wo, (pt, ct, tk)), w, False, dt, x.device)
             if ch is not None:
                 pt, ct, tk = ch
         wp = T._packed_3x3(w, False, dt, ct, x.device)
@@ -332,7 +296,7 @@ class _Conv3x3s2(torch.autograd.Function):
                 key = ("d", B * H * W, cin, cout, dys)
                 ch = T._conv3_tune.get(key)
                 if ch is None and T._rec is None:
-                    ch = T._conv3_choice(op, key, T._conv3_dgrad_cands(cin, B * H * W, (pt, ct, 0)), w, True, dt, x.device)
+                    ch = T._conv3_choice(op, key, conv_variants.conv3_dgrad_tiles(cin, B * H * W, (pt, ct, 0)), w, True, dt, x.device)
                 if ch is not None:
                     pt, ct = ch[0], ch[1]
             wp = T._packed_3x3(w, True, dt, ct, x.device)

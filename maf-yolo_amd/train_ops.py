@@ -22,7 +22,7 @@ import torch
 import torch.nn.functional as F
 
 from .config import cfg
-from . import lib, pack
+from . import conv_variants, lib, pack
 
 _DT = {torch.float16: lib.F16, torch.float32: lib.F32}
 _zeros = {}
@@ -301,7 +301,7 @@ def _ok(x, cin_mult):
 _op_cache = {}                         # launch descriptors by geometry: only the pointers change from call to call (a ctypes field store is ~0.2 us)
 
 
-def _launch_conv1x1(x, xs, wp, bias, B, H, W, cin, cout, ct, out, dt, pt=None, tk=1, bstat=None):
+def _launch_conv1x1(x, xs, wp, bias, B, H, W, cin, cout, ct, out, dt, pt=None, tk=lib.CONV_GENERIC, bstat=None):
     """bstat: (scratch, phase) of the training-mode BatchNorm behind the conv (bn_own_scratch) — the conv's epilogue accumulates its batch statistics
     (csrc/conv_stream_lds_st.hip; the caller has checked `_conv_stats_ok` for the tile)."""
     ys = out.stride()[3]
@@ -341,7 +341,7 @@ conv_bn_stats = cfg.conv_bn_stats           # A/B switch: BatchNorm statistics o
 
 def _conv_stats_ok(choice, cin, co, cout, dt, bias):
     pt, ct, tk = choice
-    return (conv_bn_stats and not _deterministic and tk == 5 and pt == 1 and dt == lib.F16 and bias is None and co == cout
+    return (conv_bn_stats and not _deterministic and tk == lib.CONV_STREAM_LDS and pt == 1 and dt == lib.F16 and bias is None and co == cout
             and bool(lib.load().maf_conv1x1_stats_supported(-(-cin // 32), ct)))
 
 
@@ -354,43 +354,13 @@ conv3_autotune = conv_autotune and cfg.train_tune3        # the 3 x 3 stride-2 l
 _conv_tune = {}
 
 
-def _stream_lds_ok(ksteps, ct):
-    from .engine import stream_lds_ok
-    return stream_lds_ok(ksteps, ct)
+_stream_lds_ok = conv_variants.stream_lds_ok          # (the name tests/test_gpu_train.py reads it by)
 
 
 def conv_candidates(M, K, Nc):
-    """(tile_p, tile_c, tile_k) of every launch `_conv_choice` times for the single-source fp16 1x1 conv K -> Nc over M pixels, in timing order: tile_p x tile_c of
-    the generic kernel, split-K, the persistent "stream" and stream + LDS forms (with the eight-wave one), LDS-shared weight fragments and their DMA ring — and
-    the static rule's tile (pack.tile_for) last if none of them is it."""
-    pt0, ct0 = pack.tile_for(Nc, M)
-    ksteps = -(-K // 32)
-    cands = []
-    for ct in (2, 4, 6, 8):
-        nt = -(-Nc // (16 * ct))
-        if nt * 16 * ct > 2 * max(Nc, 32) or (ct == 8 and Nc % 8):
-            continue
-        for pt in (1, 2, 4):
-            if (pt == 4 and ct > 4) or (pt > 1 and -(-M // (64 * pt)) * nt < 256):
-                continue
-            cands.append((pt, ct, 1))
-        if ksteps >= 8 and M <= 65536:
-            cands.append((1, ct, 4))
-        if ksteps <= 4 and ksteps * ct <= 16:
-            cands += [(1, ct, 3), (2, ct, 3)]
-        if _stream_lds_ok(ksteps, ct):
-            cands.append((1, ct, 5))
-            if ct >= 4 and 64 <= ksteps * ct <= 160 and (8 <= ksteps <= 20 or ksteps == 24):
-                cands.append((2, ct, 5))                                         # eight waves behind one LDS copy of the weights (csrc/conv_stream_lds_w8.hip)
-        if ksteps >= 4 and ct >= 4:
-            for pt in ((1, 2, 4) if ct == 4 else (1, 2)):
-                if pt == 1 or -(-M // (64 * pt)) * nt >= 256:
-                    cands.append((pt, ct, 2))
-                    if pt <= 2 and ksteps >= 8:
-                        cands.append((pt, ct, 8))                                # ... by DMA, two k-steps per barrier (csrc/conv_mfma_dma.hip)
-    if (pt0, ct0, 1) not in cands:
-        cands.append((pt0, ct0, 1))
-    return cands
+    """(tile_p, tile_c, tile_k) of every launch `_conv_choice` times for the single-source fp16 1x1 conv K -> Nc over M pixels, in timing order: what the inference
+    tuner would time for it (conv_variants.conv_tiles) and the static rule's tile (pack.tile_for) last if none of them is it."""
+    return conv_variants.with_static(conv_variants.conv_tiles(lib.OP_CONV1X1, lib.F16, M, [(K, lib.SRC_DIRECT)], Nc, Nc), (*pack.tile_for(Nc, M), lib.CONV_GENERIC))
 
 
 def _conv_choice(x, xs, B, H, W, K, Nc, dt, w2d, rows, cols, transpose, want_stats=False):
@@ -400,7 +370,7 @@ def _conv_choice(x, xs, B, H, W, K, Nc, dt, w2d, rows, cols, transpose, want_sta
     M = B * H * W
     pt0, ct0 = pack.tile_for(Nc, M)
     if not conv_autotune or dt != lib.F16 or not x.is_cuda:
-        return pt0, ct0, 1
+        return pt0, ct0, lib.CONV_GENERIC
     key = (M, K, Nc, xs, "st") if want_stats else (M, K, Nc, xs)
     best = _conv_tune.get(key)
     if best is not None:
@@ -408,29 +378,21 @@ def _conv_choice(x, xs, B, H, W, K, Nc, dt, w2d, rows, cols, transpose, want_sta
     cands = conv_candidates(M, K, Nc)
     out = _empty((B, Nc, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     torch.cuda.synchronize(x.device)                                            # a quiet chip: the side stream's weight gradients would be in the timings
-    timer, st, res, packs = lib.Timer(), _stream(x.device), [], {}
+    packs = {}
+
+    def launch(c_):
+        pt, ct, tk = c_
+        if ct not in packs:
+            packs[ct] = _packed_1x1(w2d, rows, cols, transpose, dt, ct, x.device), _zero_bias(x.device, -(-Nc // (16 * ct)) * 16 * ct)
+        _launch_conv1x1(x, xs, *packs[ct], B, H, W, K, Nc, ct, out, dt, pt, tk)
+
     global profile
     saved, profile = profile, None
     try:
-        for pt, ct, tk in cands:
-            if ct not in packs:
-                packs[ct] = _packed_1x1(w2d, rows, cols, transpose, dt, ct, x.device)
-            bp = _zero_bias(x.device, -(-Nc // (16 * ct)) * 16 * ct)
-            try:
-                _launch_conv1x1(x, xs, packs[ct], bp, B, H, W, K, Nc, ct, out, dt, pt, tk)          # warm-up (and validity)
-            except lib.MafError:
-                continue
-            ts = []
-            for _ in range(3):
-                timer.start(st)
-                _launch_conv1x1(x, xs, packs[ct], bp, B, H, W, K, Nc, ct, out, dt, pt, tk)
-                timer.stop(st)
-                ts.append(timer.elapsed_ms())
-            res.append((min(ts), pt, ct, tk))
+        res = sorted((t,) + c_ for t, c_ in conv_variants.time_candidates(launch, cands, _stream(x.device), 3, "skip"))
     finally:
         profile = saved
-    res.sort()
-    best = res[0][1:] if res else (pt0, ct0, 1)
+    best = res[0][1:] if res else (pt0, ct0, lib.CONV_GENERIC)
     if want_stats and res:
         allow = 0.006 + M * Nc * 2 / 5.0e9                                       # ms: a statistics launch alone, tools/bn_bench.py (launch + bytes / 5 TB/s)
         elig = [r for r in res if _conv_stats_ok(r[1:], K, Nc, Nc, dt, None)]

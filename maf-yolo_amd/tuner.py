@@ -10,7 +10,8 @@ import os
 import torch
 
 from .config import cfg
-from . import lib, pack
+from . import conv_variants, lib, pack
+from .conv_variants import stream_lds_ok, time_candidates      # noqa: F401  (re-exported)
 
 _TUNE_CACHE = {}          # layer signature -> (tile_p, tile_c, ...), filled by autotune
 
@@ -48,15 +49,6 @@ def choose_fusion(model, B, H, W, dtype, in_dtype, device, x, reps=3):
             _TUNE_CACHE[sigs[n]] = (min(cost, key=cost.get),)
     del plan1
     return {n: _TUNE_CACHE[sigs[n]][0] for n in names}
-
-
-def stream_lds_ok(ksteps, ct):
-    """Instantiations of the persistent 1x1 conv with LDS-resident weights (tile_k = 5: csrc/conv_stream_lds.hip, conv_stream_lds_wide.hip)."""
-    if 2 <= ksteps <= 12:
-        return ksteps * ct <= 96
-    if ct == 4 and ksteps in (26, 28, 30, 32, 34, 36, 40):          # conv_stream_lds_xwide.hip (round 6: the 832 ... 1280-channel reductions of s / m)
-        return True
-    return ct in (4, 6, 8) and (13 <= ksteps <= 20 or ksteps == 24) and ksteps * ct <= 160
 
 
 def save_tune_cache(path):
@@ -121,11 +113,11 @@ class Candidate:
 
 
 def _feeds_pairs(plan, i):
-    # a 1x1 conv whose only reader is a depth-wise conv can hand it PIXEL PAIRS — but only from the LDS-resident-weight kernel (tile_k = 5)
+    # a 1x1 conv whose only reader is a depth-wise conv can hand it PIXEL PAIRS — but only from the LDS-resident-weight kernel (CONV_STREAM_LDS)
     o = plan.ops[i]
     if not (o.kind == lib.OP_CONV1X1 and i + 1 < len(plan.ops) and plan.ops[i + 1].kind == lib.OP_DWCONV):
         return False
-    keep_tk, o.tile_k = o.tile_k, 5
+    keep_tk, o.tile_k = o.tile_k, lib.CONV_STREAM_LDS
     try:
         return plan._pairs_producer(i + 1) is not None
     finally:
@@ -148,67 +140,30 @@ def signature(plan, i):
         + (("pool1",) if r.get("pool1") else ()) + (("pairs",) if _feeds_pairs(plan, i) else ())
 
 
+_FUSED_3X3 = (lib.CONV3_LDS, lib.CONV3_WREG)      # their weight record holds the bias and does not depend on tile_c
+
+
 def packed(plan, i, wt, bt, ct, tk):
-    """(weights, bias) of conv op i packed for tile_c = ct, tile_k = tk (device tensors; one record with the bias inside for tile_k 6 / 7)."""
+    """(weights, bias) of conv op i packed for tile_c = ct, tile_k = tk (device tensors; one record with the bias inside for CONV3_LDS / CONV3_WREG)."""
     o, r = plan.ops[i], plan._ops[i]
     pool1, srcC = r.get("pool1"), r["raw"][2]
-    wp_ = ((pack.pack_mprep_wreg if tk == 7 else pack.pack_mprep_lds)(wt, bt, *pool1) if pool1 else pack.pack_conv3x3_lds(wt, bt) if tk == 6 else pack.pack_conv3x3_wreg(wt, bt) if tk == 7
+    wreg = tk == lib.CONV3_WREG
+    wp_ = ((pack.pack_mprep_wreg if wreg else pack.pack_mprep_lds)(wt, bt, *pool1) if pool1 else pack.pack_conv3x3_lds(wt, bt) if tk == lib.CONV3_LDS else pack.pack_conv3x3_wreg(wt, bt) if wreg
            else pack.pack_conv1x1(wt, srcC, ct, plan.dtype) if o.kind == lib.OP_CONV1X1 else pack.pack_conv3x3(wt, ct, plan.dtype)).to(plan.device)
-    return wp_, pack.pack_bias(bt, ct if tk not in (6, 7) else 4).to(plan.device)
+    return wp_, pack.pack_bias(bt, ct if tk not in _FUSED_3X3 else 4).to(plan.device)
 
 
 def conv_tiles(plan, i):
-    """(tile_p, tile_c, tile_k) of every variant the tuner times for conv op i (OP_CONV1X1 / OP_CONV3X3S2), in timing order."""
+    """(tile_p, tile_c, tile_k) of every variant the tuner times for conv op i (OP_CONV1X1 / OP_CONV3X3S2), in timing order: conv_variants.conv_tiles of the op."""
     o, r = plan.ops[i], plan._ops[i]
-    M = plan.B * o.H * o.W
-    twin, pool1 = r.get("twin"), r.get("pool1")
-    cands = []
-    for ct in (2, 4, 6, 8):
-        nt = -(-o.Cout // (16 * ct))
-        if nt * 16 * ct > 2 * max(o.Cout, 32) or (ct == 8 and o.out_stride % 8 and not o.out_f32 and plan.dtype == lib.F16):
-            continue
-        for pt in (1, 2, 4):
-            if pt == 4 and ct > 4:
-                continue
-            if -(-M // (64 * pt)) * nt < 256 and pt > 1:
-                continue                          # would not fill the chip
-            cands.append((pt, ct, 1))
-        ksteps = sum(-(-o.src[k].C // (32 if plan.dtype == lib.F16 else 16)) for k in range(o.nsrc)) * (9 if o.kind == lib.OP_CONV3X3S2 else 1)
-        if ksteps >= 8 and M <= 65536:
-            cands.append((1, ct, 4))                 # split-K across the 4 waves: long reductions on small maps
-        direct = o.kind == lib.OP_CONV1X1 and o.nsrc == 1 and o.src[0].mode == lib.SRC_DIRECT
-        if direct and plan.dtype == lib.F16 and not o.out_f32 and ksteps <= 4 and ksteps * ct <= 16:
-            for pt in (1, 2):                                # persistent waves, next tile's activations in flight during the epilogue
-                cands.append((pt, ct, 3))
-        if o.kind == lib.OP_CONV1X1 and plan.dtype == lib.F16 and not o.out_f32 and stream_lds_ok(ksteps, ct) \
-                and (o.nsrc == 1 or all(o.src[k].mode != lib.SRC_POOL2 for k in range(o.nsrc))) and (direct or ct >= 4 or o.nsrc == 1):
-            cands.append((1, ct, 5))                         # persistent waves, the channel tile's weights resident in LDS
-            if ct >= 4 and 64 <= ksteps * ct <= 160 and (8 <= ksteps <= 20 or ksteps == 24):
-                cands.append((2, ct, 5))                     # ... eight waves behind one copy of the weights where the LDS leaves room for one or two workgroups per CU (conv_stream_lds_w8.hip)
-        if o.kind == lib.OP_CONV3X3S2 and plan.dtype == lib.F16 and (o.Cin, o.Cout) in ((48, 48), (48, 64), (64, 64)) and ct == 4 and (M >= 65536 or pool1):
-            for wg in (4, 8, 12, 16):                         # weights + input patch in LDS, 256 .. 1024 persistent workgroups (tile_c = workgroups / 64)
-                cands.append((4, wg, 6))
-        if o.kind == lib.OP_CONV3X3S2 and plan.dtype == lib.F16 and pack.conv3x3_wreg_shape(o.Cin, o.Cout) and ct == 4:
-            for wg in (2, 4, 8):                              # weights in registers, patches by DMA: 64 / 128 / 256 workgroups per conv (tile_c = that / 32)
-                if wg * 32 * (2 if twin else 1) <= 256:
-                    cands += [(3, wg, 7), (2, wg, 7)]         # tile_p = patch buffers (3: two patches in flight ahead of the multiply)
-        pooled = o.nsrc == 1 and o.src[0].mode == lib.SRC_POOL2
-        if ksteps >= 4 and ct >= 4 and plan.dtype == lib.F16 and not o.out_f32 and not pooled:
-            for pt in ((1, 2, 4) if ct == 4 else (1, 2)):     # the workgroup shares each k-step's weight fragments through LDS
-                if pt == 1 or -(-M // (64 * pt)) * nt >= 256:
-                    cands.append((pt, ct, 2))
-                    if pt <= 2 and ksteps >= 8:                # ... that arrive by DMA, two k-steps per barrier, three stages ahead (K-heavy layers)
-                        cands.append((pt, ct, 8))
-    if twin:
-        cands = [c_ for c_ in cands if c_[2] in (1, 2, 4, 7, 8)] # the variants that take a twin launch
-    if pool1:
-        cands = [c_ for c_ in cands if c_[2] == r.get("pool1_tk", 6)]   # only the workgroup count (and the patch buffers of tile_k = 7) are open
-    return cands
+    return conv_variants.conv_tiles(o.kind, plan.dtype, plan.B * o.H * o.W, [(o.src[k].C, o.src[k].mode) for k in range(o.nsrc)], o.Cout, o.out_stride, bool(o.out_f32),
+                                    bool(r.get("twin")), r.get("pool1_tk", lib.CONV3_LDS) if r.get("pool1") else None)
 
 
 def dw_tiles(plan, i):
     """(tile_p, tile_c, tile_k) of every variant the tuner times for depth-wise op i, in timing order: the v_fma_mix kernel's (rows, columns, channel block), then
-    dot2 (tile_p = -2), pixel pairs (tile_p = -4; only where the 1x1 conv in front, as the plan stands, can store pairs) and the matrix-core form (tile_p = -1)."""
+    dot2 (DW_DOT2), pixel pairs (DW_PAIRS; only where the 1x1 conv in front, as the plan stands, can store pairs) and the matrix-core form (DW_MFMA); the tile_k
+    of dot2 / pairs: lib.dw_tile_k."""
     o = plan.ops[i]
     n = 8 if plan.dtype == lib.F16 else 4
     out = []
@@ -224,7 +179,7 @@ def dw_tiles(plan, i):
                 if lds > 96 * 1024 or (t_h, t_w, cb) in out:
                     continue
                 out.append((t_h, t_w, cb))
-    if plan.dtype == lib.F16:                            # two taps per instruction (csrc/dwconv_dot2.hip): tile_p = -2, tile_c = columns, tile_k = rows * 256 + channels
+    if plan.dtype == lib.F16:                            # two taps per instruction (csrc/dwconv_dot2.hip): tile_c = columns, tile_k = rows, channels
         w8 = -(-o.W // 8) * 8
         for th in sorted({4, 8, 10, 16, 20} | ({o.H} if o.H <= 40 else set())):
             if th > o.H:
@@ -236,10 +191,10 @@ def dw_tiles(plan, i):
                     cb = min(cb, o.Cin)
                     nq, np_ = cb // 4, (o.ksize + 1) // 2
                     lds = ((th + o.ksize - 1) * ((tw + o.ksize - 1) // 2) * (nq + 3) + o.ksize * 2 * np_ * nq) * 16      # (pair stride <= nq + 3: csrc/dwconv_dot2.hip)
-                    if lds > 96 * 1024 or (-2, tw, th * 256 + cb) in out:
+                    if lds > 96 * 1024 or (lib.DW_DOT2, tw, lib.dw_tile_k(th, cb)) in out:
                         continue
-                    out.append((-2, tw, th * 256 + cb))
-    if plan._pairs_producer(i) is not None:              # pixel-pair input, v_dot2c with scalar weight pairs (csrc/dwconv_p2.hip): tile_p = -4, tile_c = columns, tile_k = rows * 256 + waves per workgroup
+                    out.append((lib.DW_DOT2, tw, lib.dw_tile_k(th, cb)))
+    if plan._pairs_producer(i) is not None:              # pixel-pair input, v_dot2c with scalar weight pairs (csrc/dwconv_p2.hip): tile_c = columns, tile_k = rows, waves per workgroup
         w4 = -(-o.W // 4) * 4
         for th in sorted({4, 5, 8, 10, 16, 20} | ({o.H} if o.H <= 40 else set())):
             if th > o.H:
@@ -250,14 +205,14 @@ def dw_tiles(plan, i):
                 plane = p2_wave_bytes(th, tw, o.ksize)
                 if plane > 20 * 1024:                    # fewer than 8 waves per CU: never the fastest
                     continue
-                for nw, stg in ((2, 0), (4, 0), (8, 0), (2, 128), (4, 128), (8, 128)):
-                    # + 128: staged stores (the waves of a workgroup = adjacent channel groups of one tile, results through the dead planes,
+                for nw, stg in ((2, False), (4, False), (8, False), (2, True), (4, True), (8, True)):
+                    # staged stores (the waves of a workgroup = adjacent channel groups of one tile, results through the dead planes,
                     # nw x 16-byte runs per pixel): where the kernel takes that form (csrc/dwconv_p2.hip:maf_launch_dwconv_p2)
                     if stg and not ((o.Cin // 8) % nw == 0 and th * (tw // 4) <= 64 and plane >= 4160 and o.Cout <= 2 * o.Cin and _P2_STAGE):
                         continue
-                    out.append((-4, tw, th * 256 + nw + stg))
-    if plan.dtype == lib.F16 and o.aux[0]:               # matrix-core variant (csrc/dwconv_mfma.hip): tile_p = -1
-        out.append((-1, 0, 0))
+                    out.append((lib.DW_PAIRS, tw, lib.dw_tile_k(th, nw, stg)))
+    if plan.dtype == lib.F16 and o.aux[0]:               # matrix-core variant (csrc/dwconv_mfma.hip)
+        out.append((lib.DW_MFMA, 0, 0))
     return out
 
 
@@ -265,7 +220,7 @@ def candidates(plan, i):
     """Every launch the tuner times for op i of `plan`, in timing order (a list of `Candidate`; empty for an op it does not time).  Stem pairs: tile height (8 / 4
     rows; 4 only for the 48 -> 96 stem, whose kernel takes no other) x persistent workgroups; head tails: persistent iterations per CU; depth-wise: `dw_tiles`;
     1x1 and 3x3 stride-2 convs: `conv_tiles`, each with its own weight packing.  The list of a depth-wise op depends on the tile_k its producer holds (pixel pairs
-    only behind tile_k = 5), so it is what the tuner offers at the point it reaches op i.  The stem's image (src[0].ptr) and the head tail's output are the plan
+    only behind CONV_STREAM_LDS), so it is what the tuner offers at the point it reaches op i.  The stem's image (src[0].ptr) and the head tail's output are the plan
     op's: the caller points them at real buffers."""
     o, r = plan.ops[i], plan._ops[i]
     if o.kind == lib.OP_STEM2:
@@ -288,8 +243,8 @@ def candidates(plan, i):
         for tp, tc, tk in dw_tiles(plan, i):
             op = lib.MafOp.from_buffer_copy(o)
             op.tile_p, op.tile_c, op.tile_k = tp, tc, tk
-            op.src[0].mode = lib.SRC_PAIRS if tp == -4 else lib.SRC_DIRECT
-            out.append(Candidate((tp, tc, tk), op, pairs=tp == -4))
+            op.src[0].mode = lib.SRC_PAIRS if tp == lib.DW_PAIRS else lib.SRC_DIRECT
+            out.append(Candidate((tp, tc, tk), op, pairs=tp == lib.DW_PAIRS))
         return out
     if o.kind not in (lib.OP_CONV1X1, lib.OP_CONV3X3S2):
         return []
@@ -297,7 +252,7 @@ def candidates(plan, i):
     twin = r.get("twin")
     packs, out = {}, []
     for pt, ct, tk in conv_tiles(plan, i):
-        form = (ct if tk not in (6, 7) else 0, tk if tk in (6, 7) else 0)
+        form = (0, tk) if tk in _FUSED_3X3 else (ct, 0)
         if form not in packs:
             packs[form] = packed(plan, i, w, b, ct, tk) + (packed(plan, i, *twin["raw"], ct, tk) if twin else ())
         keep = packs[form]
@@ -320,22 +275,12 @@ def autotune(plan, x, reps=5, verbose=False):
     pred = torch.empty(plan.B, plan.A, 5 + plan.nc, dtype=torch.float32, device=plan.device)
     plan.run_into(x, pred)                                   # every buffer holds realistic data
     torch.cuda.synchronize(plan.device)
-    timer = lib.Timer()
     plan._tuned = getattr(plan, "_tuned", [])
     changed = 0
 
     def timed(cands):
-        res = []
-        for c_ in cands:
-            lib.check(L.maf_op_launch(C.byref(c_.op), stream.cuda_stream))          # warm-up
-            ts = []
-            for _ in range(reps):
-                timer.start(stream.cuda_stream)
-                lib.check(L.maf_op_launch(C.byref(c_.op), stream.cuda_stream))
-                timer.stop(stream.cuda_stream)
-                ts.append(timer.elapsed_ms())
-            res.append((min(ts),) + c_.tiles)
-        return res
+        res = time_candidates(lambda c_: lib.check(L.maf_op_launch(C.byref(c_.op), stream.cuda_stream)), cands, stream.cuda_stream, reps, "raise")
+        return [(t,) + c_.tiles for t, c_ in res]
 
     for i, (o, r) in enumerate(zip(plan.ops, plan._ops)):
         sig = signature(plan, i)
@@ -371,17 +316,17 @@ def autotune(plan, x, reps=5, verbose=False):
                 results = sorted(timed(candidates(plan, i)))     # (pixel-pair candidates read the NHWC content of the buffer as pairs: same work)
                 best = results[0][1:]
                 _TUNE_CACHE[sig] = best
-                _TUNE_CACHE[sig + ("nhwc",)] = [r_ for r_ in results if r_[1] != -4][0][1:]      # for a plan whose producer cannot store pixel pairs
+                _TUNE_CACHE[sig + ("nhwc",)] = [r_ for r_ in results if r_[1] != lib.DW_PAIRS][0][1:]      # for a plan whose producer cannot store pixel pairs
                 if verbose:
                     print("tune %-32s %dx%d C=%d k=%d: %s" % (plan.op_names[i], o.H, o.W, o.Cin, o.ksize, " ".join("(%d,%d,%d)%.1fus" % (a, b2, c2, t * 1e3) for t, a, b2, c2 in results[:6])))
-                    p2 = [r_ for r_ in results if r_[1] == -4]
-                    if any(r_[3] & 128 for r_ in p2):                # pixel-pair kernel: best tile with plain / staged stores
-                        bu, bs = [r_ for r_ in p2 if not r_[3] & 128][0], [r_ for r_ in p2 if r_[3] & 128][0]
-                        print("     dwconv_p2 stores  plain (%d,%d) %.1fus   staged (%d,%d) %.1fus" % (bu[2], bu[3], bu[0] * 1e3, bs[2], bs[3] - 128, bs[0] * 1e3))
+                    p2 = [r_ for r_ in results if r_[1] == lib.DW_PAIRS]
+                    if any(r_[3] & lib.DW_P2_STAGED for r_ in p2):   # pixel-pair kernel: best tile with plain / staged stores
+                        bu, bs = [r_ for r_ in p2 if not r_[3] & lib.DW_P2_STAGED][0], [r_ for r_ in p2 if r_[3] & lib.DW_P2_STAGED][0]
+                        print("     dwconv_p2 stores  plain (%d,%d) %.1fus   staged (%d,%d) %.1fus" % (bu[2], bu[3], bu[0] * 1e3, bs[2], bs[3] - lib.DW_P2_STAGED, bs[0] * 1e3))
             prod = plan._pairs_producer(i)
-            if best[0] == -4 and prod is None:
+            if best[0] == lib.DW_PAIRS and prod is None:
                 best = _TUNE_CACHE.get(sig + ("nhwc",), (0, 0, 0))
-            pairs = 1 if best[0] == -4 else 0
+            pairs = 1 if best[0] == lib.DW_PAIRS else 0
             if tuple(best) != (o.tile_p, o.tile_c, o.tile_k) or (prod is not None and prod.out_pairs != pairs):
                 o.tile_p, o.tile_c, o.tile_k = best
                 o.src[0].mode = lib.SRC_PAIRS if pairs else lib.SRC_DIRECT
@@ -393,17 +338,17 @@ def autotune(plan, x, reps=5, verbose=False):
         if best is None:
             results = sorted(timed(candidates(plan, i)))
             best = (results[0][1], results[0][2], results[0][3])
-            # where pairs are possible (signature: "pairs"), tile_k = 5 is kept unless another variant is clearly (1.3x) faster.  Timed alone, the register-weight form
+            # where pairs are possible (signature: "pairs"), CONV_STREAM_LDS is kept unless another variant is clearly (1.3x) faster.  Timed alone, the register-weight form
             # sometimes wins such a layer by a few hundred nanoseconds (run-to-run noise) and the depth-wise conv behind it then loses its pair input
             # (n, 20 x 20 x 288, k = 9: 20.9 -> 27.9 us)
             if sig[-1] == "pairs":
-                five = [r_ for r_ in results if r_[3] == 5]
+                five = [r_ for r_ in results if r_[3] == lib.CONV_STREAM_LDS]
                 if five and five[0][0] <= 1.3 * results[0][0]:
                     best = (five[0][1], five[0][2], five[0][3])
             _TUNE_CACHE[sig] = best
             if verbose:
                 M = plan.B * o.H * o.W
-                print("tune %-32s M=%-7d %4d->%-4d: %s" % (plan.op_names[i], M, o.Cin, o.Cout, " ".join("(%d,%d%s)%.1fus" % (p, c, {4: ",k4", 2: ",lds", 3: ",stream", 5: ",streamlds", 6: ",ldsall", 7: ",wreg", 8: ",dma"}.get(k, ""), t * 1e3) for t, p, c, k in results)))
+                print("tune %-32s M=%-7d %4d->%-4d: %s" % (plan.op_names[i], M, o.Cin, o.Cout, " ".join("(%d,%d%s)%.1fus" % (p, c, "," + lib.CONV_VARIANT_NAMES[k] if k > lib.CONV_GENERIC else "", t * 1e3) for t, p, c, k in results)))
         pt, ct, tk = best
         if pool1:
             if (pt, ct) != (o.tile_p, o.tile_c):

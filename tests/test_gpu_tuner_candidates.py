@@ -14,7 +14,7 @@ import pytest
 import torch
 
 import maf_yolo_amd as M
-from maf_yolo_amd import engine, lib, pack, tuner
+from maf_yolo_amd import engine, lib, pack, train_ops, tuner
 from oracle import maf_oracle as O
 import op_ref
 
@@ -23,7 +23,7 @@ DEV = torch.device("cuda:0")
 SENT = 1234.0
 _KIND = {lib.OP_CONV1X1: "conv1x1", lib.OP_CONV3X3S2: "conv3x3s2", lib.OP_DWCONV: "dwconv", lib.OP_STEM2: "stem2", lib.OP_BOTTLENECK: "bottleneck",
          lib.OP_CONV1DW: "conv1dw", lib.OP_SPPF_POOL: "sppf pool", lib.OP_HEADTAIL: "headtail"}
-_TK = {1: "generic", 2: "lds", 3: "stream", 4: "split-k", 5: "stream+lds", 6: "ldsall", 7: "wreg", 8: "dma ring"}
+_TK = lib.CONV_VARIANT_NAMES
 
 
 def _launch(op):
@@ -340,3 +340,41 @@ def test_frozen_tables_pick_candidates_and_their_plans_predict_alike(scale, tabl
     np.testing.assert_allclose(got[..., 4:], base[..., 4:], rtol=0, atol=2 * score_atol)
     oracle = O.predict(O.reparam(O.synth_state_dict(scale, 0), scale), scale, x[:2].float().cpu()).numpy()
     _close16(got[:2], oracle, scale)
+
+
+def test_time_candidates_skips_or_raises_a_rejected_launch():
+    """tuner.time_candidates under the two policies of its call sites, at the smallest 1x1 conv that reaches both (1 x 4 x 4, 64 -> 32): the generic kernel, and
+    CONV_STREAM_LDS with tile_c = 3, which the dispatcher turns down while it checks its arguments (MAF_E_UNSUPPORTED: nothing is launched).  The training
+    tuners skip such a candidate, the inference tuner raises."""
+    B, H, W, cin, cout = 1, 4, 4, 64, 32
+    cands = [(1, 2, lib.CONV_GENERIC), (1, 3, lib.CONV_STREAM_LDS)]
+    torch.manual_seed(0)
+    x = torch.randn(B, cin, H, W, device=DEV).half().contiguous(memory_format=torch.channels_last)
+    w = torch.randn(cout, cin, device=DEV) / cin ** 0.5
+    out = torch.zeros(B, cout, H, W, device=DEV, dtype=torch.float16).contiguous(memory_format=torch.channels_last)
+    wp, bp = train_ops._packed_1x1(w.contiguous(), cout, cin, 0, lib.F16, 2, DEV), train_ops._zero_bias(DEV, 64)
+    st = train_ops._stream(DEV)
+
+    def train_launch(c_):
+        train_ops._launch_conv1x1(x, cin, wp, bp, B, H, W, cin, cout, c_[1], out, lib.F16, c_[0], c_[2])
+
+    res = tuner.time_candidates(train_launch, cands, st, 3, "skip")
+    torch.cuda.synchronize(DEV)
+    assert len(res) == 1 and res[0][1] == cands[0] and res[0][0] > 0, res
+    ref = torch.nn.functional.conv2d(x.float(), w.half().float().reshape(cout, cin, 1, 1))
+    assert (out.float() - ref).abs().max().item() <= 2e-3 * ref.abs().max().item() + 2e-3
+
+    ops = []
+    for pt, ct, tk in cands:
+        op = lib.MafOp()
+        op.kind, op.dtype, op.in_dtype, op.act = lib.OP_CONV1X1, lib.F16, lib.F16, lib.ACT_NONE
+        op.B, op.H, op.W, op.Cin, op.Cout, op.nsrc = B, H, W, cin, cout, 1
+        op.src[0].ptr, op.src[0].C, op.src[0].stride, op.src[0].mode = x.data_ptr(), cin, cin, lib.SRC_DIRECT
+        op.out, op.out_stride, op.w, op.bias = out.data_ptr(), cout, wp.data_ptr(), bp.data_ptr()
+        op.tile_p, op.tile_c, op.tile_k = pt, ct, tk
+        ops.append(op)
+    L = lib.load()
+    assert L.maf_op_launch(C.byref(ops[1]), st) == -2                  # MAF_E_UNSUPPORTED
+    with pytest.raises(lib.MafError):
+        tuner.time_candidates(lambda op: lib.check(L.maf_op_launch(C.byref(op), st)), ops, st, 5, "raise")
+    torch.cuda.synchronize(DEV)

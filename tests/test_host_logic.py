@@ -44,6 +44,21 @@ def test_struct_layout_matches_header(built):
     assert int(a) == ctypes.sizeof(lib.MafSrc) and int(b) == ctypes.sizeof(lib.MafOp)
 
 
+def test_variant_selectors_match_header():
+    # every MAF_CONV_* / MAF_CONV3_* / MAF_DW_* value of the header == its lib.py mirror, and the depth-wise tile_k word packs and unpacks
+    text = open(os.path.join(ROOT, "include", "mafyolo_hip.h")).read()
+    names = dict(re.findall(r"\b(MAF_(?:CONV3?|DW)_[A-Z0-9_]+) = (-?\d+)", text))
+    assert len(names) == 12 and {"MAF_CONV_GENERIC", "MAF_CONV3_WREG", "MAF_CONV_DMA", "MAF_DW_PAIRS", "MAF_DW_P2_STAGED"} <= set(names)
+    for name, value in names.items():
+        assert getattr(lib, name[len("MAF_"):]) == int(value), name
+    assert set(lib.CONV_VARIANT_NAMES) == {int(v) for n, v in names.items() if n.startswith("MAF_CONV")}
+    for rows in range(4, 41):
+        for n in range(1, 9):
+            for staged in (False, True):
+                assert lib.dw_tile_k_split(lib.dw_tile_k(rows, n, staged)) == (rows, n, staged)
+    assert lib.dw_tile_k(20, 4, True) == 20 * 256 + 4 + 128 and lib.dw_tile_k_split(10 * 256 + 64) == (10, 64, False)
+
+
 def test_error_reporting_without_gpu(built):
     op = lib.MafOp()
     op.kind = 99

@@ -6,7 +6,7 @@ from types import SimpleNamespace
 import pytest
 import torch
 
-from maf_yolo_amd import lib, train_ops, tuner
+from maf_yolo_amd import conv_variants, lib, pack, train_ops, tuner
 
 
 def _op(kind, B, H, W, cin, cout, srcs=None, ksize=0, out_stride=None, out_f32=0, act=lib.ACT_SILU):
@@ -94,7 +94,6 @@ def test_train_enumerator(M_hw, cin, cout):
     cands = train_ops.conv_candidates(M, cin, cout)
     ksteps = -(-cin // 32)
     assert len(set(cands)) == len(cands) >= 6
-    from maf_yolo_amd import pack
     assert (*pack.tile_for(cout, M), 1) in cands                           # the static rule's tile is always timed
     for pt, ct, tk in cands:
         assert tk in (1, 2, 3, 4, 5, 8) and ct in (2, 4, 6, 8) and pt in (1, 2, 4)
@@ -128,3 +127,77 @@ _TRAIN_LISTS = {
 def test_train_enumerator_lists_are_pinned():
     for (M, K, N), want in _TRAIN_LISTS.items():
         assert train_ops.conv_candidates(M, K, N) == want, (M, K, N)
+
+
+# tuner.conv_tiles for _CONVS, keyed like them, as the commit before conv_variants.py returned them (three enumerators, one per tuner): whole lists, order included
+_INFER_LISTS = {
+    (1, 32, 160, 160, 48, 48): [(1, 2, 1), (2, 2, 1), (4, 2, 1), (1, 2, 3), (2, 2, 3), (1, 2, 5), (1, 4, 1), (2, 4, 1), (4, 4, 1), (1, 4, 3), (2, 4, 3), (1, 4, 5), (1, 6, 1), (2, 6, 1), (1, 6, 3), (2, 6, 3), (1, 6, 5)],
+    (1, 32, 20, 20, 288, 96): [(1, 2, 1), (2, 2, 1), (1, 2, 4), (1, 2, 5), (1, 4, 1), (1, 4, 4), (1, 4, 5), (1, 4, 2), (1, 4, 8), (1, 6, 1), (1, 6, 4), (1, 6, 5), (1, 6, 2), (1, 6, 8), (1, 8, 1), (1, 8, 4), (1, 8, 5), (2, 8, 5), (1, 8, 2), (1, 8, 8)],
+    (1, 1, 20, 20, 1280, 640): [(1, 2, 1), (1, 2, 4), (1, 4, 1), (1, 4, 4), (1, 4, 5), (1, 4, 2), (1, 4, 8), (1, 6, 1), (1, 6, 4), (1, 6, 2), (1, 6, 8), (1, 8, 1), (1, 8, 4), (1, 8, 2), (1, 8, 8)],
+    (1, 32, 40, 40, 640, 192): [(1, 2, 1), (2, 2, 1), (4, 2, 1), (1, 2, 4), (1, 4, 1), (2, 4, 1), (4, 4, 1), (1, 4, 4), (1, 4, 5), (2, 4, 5), (1, 4, 2), (1, 4, 8), (2, 4, 2), (2, 4, 8), (4, 4, 2), (1, 6, 1), (2, 6, 1), (1, 6, 4), (1, 6, 5), (2, 6, 5), (1, 6, 2), (1, 6, 8), (2, 6, 2), (2, 6, 8), (1, 8, 1), (2, 8, 1), (1, 8, 4), (1, 8, 5), (2, 8, 5), (1, 8, 2), (1, 8, 8), (2, 8, 2), (2, 8, 8)],
+    (1, 3, 11, 19, 448, 128): [(1, 2, 1), (1, 2, 4), (1, 4, 1), (1, 4, 4), (1, 4, 5), (1, 4, 2), (1, 4, 8), (1, 6, 1), (1, 6, 4), (1, 6, 5), (2, 6, 5), (1, 6, 2), (1, 6, 8), (1, 8, 1), (1, 8, 4), (1, 8, 5), (2, 8, 5), (1, 8, 2), (1, 8, 8)],
+    (2, 32, 80, 80, 48, 64): [(1, 2, 1), (2, 2, 1), (4, 2, 1), (1, 4, 1), (2, 4, 1), (4, 4, 1), (4, 4, 6), (4, 8, 6), (4, 12, 6), (4, 16, 6), (1, 4, 2), (1, 4, 8), (2, 4, 2), (2, 4, 8), (4, 4, 2), (1, 6, 1), (2, 6, 1), (1, 6, 2), (1, 6, 8), (2, 6, 2), (2, 6, 8), (1, 8, 1), (2, 8, 1), (1, 8, 2), (1, 8, 8), (2, 8, 2), (2, 8, 8)],
+    (2, 32, 40, 40, 96, 96): [(1, 2, 1), (2, 2, 1), (4, 2, 1), (1, 2, 4), (1, 4, 1), (2, 4, 1), (4, 4, 1), (1, 4, 4), (3, 2, 7), (2, 2, 7), (3, 4, 7), (2, 4, 7), (3, 8, 7), (2, 8, 7), (1, 4, 2), (1, 4, 8), (2, 4, 2), (2, 4, 8), (4, 4, 2), (1, 6, 1), (2, 6, 1), (1, 6, 4), (1, 6, 2), (1, 6, 8), (2, 6, 2), (2, 6, 8), (1, 8, 1), (2, 8, 1), (1, 8, 4), (1, 8, 2), (1, 8, 8), (2, 8, 2), (2, 8, 8)],
+    (2, 1, 10, 10, 384, 384): [(1, 2, 1), (1, 2, 4), (1, 4, 1), (1, 4, 4), (1, 4, 2), (1, 4, 8), (1, 6, 1), (1, 6, 4), (1, 6, 2), (1, 6, 8), (1, 8, 1), (1, 8, 4), (1, 8, 2), (1, 8, 8)],
+    (1, 32, 80, 80, 256, 68): [(1, 2, 1), (2, 2, 1), (4, 2, 1), (1, 2, 5), (1, 4, 1), (2, 4, 1), (4, 4, 1), (1, 4, 5), (1, 4, 2), (1, 4, 8), (2, 4, 2), (2, 4, 8), (4, 4, 2), (1, 6, 1), (2, 6, 1), (1, 6, 5), (1, 6, 2), (1, 6, 8), (2, 6, 2), (2, 6, 8)],
+}
+# ... for the two cases of test_conv_candidates_with_multiple_sources_and_pooling, a twin launch, MPRep in one launch on either 3x3 kernel and an fp32 plan
+_INFER_SPECIAL = {
+    'up2+direct': [(1, 2, 1), (2, 2, 1), (4, 2, 1), (1, 2, 4), (1, 4, 1), (2, 4, 1), (4, 4, 1), (1, 4, 4), (1, 4, 5), (1, 4, 2), (1, 4, 8), (2, 4, 2), (2, 4, 8), (4, 4, 2), (1, 6, 1), (2, 6, 1), (1, 6, 4), (1, 6, 5), (2, 6, 5), (1, 6, 2), (1, 6, 8), (2, 6, 2), (2, 6, 8), (1, 8, 1), (2, 8, 1), (1, 8, 4), (1, 8, 5), (2, 8, 5), (1, 8, 2), (1, 8, 8), (2, 8, 2), (2, 8, 8)],
+    'pooled': [(1, 2, 1), (2, 2, 1), (4, 2, 1), (1, 2, 5), (1, 4, 1), (2, 4, 1), (4, 4, 1), (1, 4, 5), (1, 6, 1), (2, 6, 1), (1, 6, 5), (1, 8, 1), (2, 8, 1), (1, 8, 5)],
+    'twin': [(1, 2, 1), (2, 2, 1), (4, 2, 1), (1, 4, 1), (2, 4, 1), (4, 4, 1), (1, 4, 2), (2, 4, 2), (4, 4, 2), (1, 6, 1), (2, 6, 1), (1, 6, 2), (2, 6, 2), (1, 8, 1), (2, 8, 1), (1, 8, 2), (2, 8, 2)],
+    'pool1_tk6': [(4, 4, 6), (4, 8, 6), (4, 12, 6), (4, 16, 6)],
+    'pool1_tk7': [(3, 2, 7), (2, 2, 7), (3, 4, 7), (2, 4, 7), (3, 8, 7), (2, 8, 7)],
+    'fp32': [(1, 2, 1), (1, 4, 1), (1, 6, 1), (1, 8, 1)],
+}
+# (M, cin, cout) -> (forward list, data-gradient list) of the training 3x3 stride-2 tuner, from the same commit
+_TRAIN3_LISTS = {
+    (204800, 48, 64): ([(1, 2, 1), (2, 2, 1), (4, 2, 1), (1, 4, 1), (2, 4, 1), (4, 4, 1), (1, 4, 2), (1, 4, 8), (2, 4, 2), (2, 4, 8), (4, 4, 2), (1, 6, 1), (2, 6, 1), (1, 6, 2), (1, 6, 8), (2, 6, 2), (2, 6, 8), (1, 8, 1), (2, 8, 1), (1, 8, 2), (1, 8, 8), (2, 8, 2), (2, 8, 8)],
+        [(1, 2, 0), (2, 2, 0), (4, 2, 0), (1, 4, 0), (2, 4, 0), (4, 4, 0)]),
+    (51200, 96, 96): ([(1, 2, 1), (2, 2, 1), (4, 2, 1), (1, 2, 4), (1, 4, 1), (2, 4, 1), (4, 4, 1), (1, 4, 4), (1, 4, 2), (1, 4, 8), (2, 4, 2), (2, 4, 8), (4, 4, 2), (1, 6, 1), (2, 6, 1), (1, 6, 4), (1, 6, 2), (1, 6, 8), (2, 6, 2), (2, 6, 8), (1, 8, 1), (2, 8, 1), (1, 8, 4), (1, 8, 2), (1, 8, 8), (2, 8, 2), (2, 8, 8)],
+        [(1, 2, 0), (2, 2, 0), (4, 2, 0), (1, 4, 0), (2, 4, 0), (1, 8, 0)]),
+    (100, 384, 384): ([(1, 2, 1), (1, 2, 4), (1, 4, 1), (1, 4, 4), (1, 4, 2), (1, 4, 8), (1, 6, 1), (1, 6, 4), (1, 6, 2), (1, 6, 8), (1, 8, 1), (1, 8, 4), (1, 8, 2), (1, 8, 8)],
+        [(1, 2, 0), (1, 4, 0), (1, 8, 0)]),
+    (3200, 128, 128): ([(1, 2, 1), (1, 2, 4), (1, 4, 1), (1, 4, 4), (1, 4, 2), (1, 4, 8), (1, 6, 1), (1, 6, 4), (1, 6, 2), (1, 6, 8), (1, 8, 1), (1, 8, 4), (1, 8, 2), (1, 8, 8)],
+        [(1, 2, 0), (1, 4, 0), (1, 8, 0)]),
+    (128, 64, 64): ([(1, 2, 1), (1, 2, 4), (1, 4, 1), (1, 4, 4), (1, 4, 2), (1, 4, 8), (1, 6, 1), (1, 6, 4), (1, 6, 2), (1, 6, 8), (1, 8, 1), (1, 8, 4), (1, 8, 2), (1, 8, 8)],
+        [(1, 2, 0), (1, 4, 0), (1, 8, 0)]),
+}
+
+
+@pytest.mark.parametrize("conv", _CONVS)
+def test_inference_enumerator_lists_are_pinned(conv):
+    assert tuner.conv_tiles(_conv_plan(*conv), 0) == _INFER_LISTS[conv]
+
+
+def _special_plan(kind, B, H, W, cin, cout, rec=None, dtype=lib.F16, **kw):
+    plan = _conv_plan(kind, B, H, W, cin, cout, **kw)
+    plan._ops[0].update(rec or {})
+    plan.dtype = plan.ops[0].dtype = dtype
+    return plan
+
+
+def test_inference_enumerator_special_lists_are_pinned():
+    plans = {
+        "up2+direct": _special_plan(lib.OP_CONV1X1, 32, 40, 40, 384, 128, srcs=[(128, lib.SRC_UP2), (256, lib.SRC_DIRECT)]),
+        "pooled": _special_plan(lib.OP_CONV1X1, 32, 80, 80, 64, 64, srcs=[(64, lib.SRC_POOL2)]),
+        "twin": _special_plan(lib.OP_CONV1X1, 32, 40, 40, 128, 128, rec=dict(twin=dict(raw=None))),
+        "pool1_tk6": _special_plan(lib.OP_CONV3X3S2, 32, 80, 80, 48, 48, rec=dict(pool1=(1,), pool1_tk=lib.CONV3_LDS)),
+        "pool1_tk7": _special_plan(lib.OP_CONV3X3S2, 32, 80, 80, 96, 96, rec=dict(pool1=(1,), pool1_tk=lib.CONV3_WREG)),
+        "fp32": _special_plan(lib.OP_CONV1X1, 1, 20, 20, 64, 64, dtype=lib.F32),
+    }
+    assert set(plans) == set(_INFER_SPECIAL)
+    for name, plan in plans.items():
+        assert tuner.conv_tiles(plan, 0) == _INFER_SPECIAL[name], name
+    assert {t[2] for t in _INFER_SPECIAL["fp32"]} <= {lib.CONV_GENERIC, lib.CONV_SPLITK}
+    assert {t[2] for t in _INFER_SPECIAL["twin"]} <= {lib.CONV_GENERIC, lib.CONV_LDS, lib.CONV_SPLITK, lib.CONV3_WREG, lib.CONV_DMA}
+
+
+@pytest.mark.parametrize("M,cin,cout", list(_TRAIN3_LISTS))
+def test_train_3x3_enumerator_lists_are_pinned(M, cin, cout):
+    fwd, dgrad = _TRAIN3_LISTS[(M, cin, cout)]
+    assert train_ops._conv3_fwd_cands(cin, cout, M, (*pack.tile_for(cout, M), lib.CONV_GENERIC)) == fwd
+    assert conv_variants.conv3_dgrad_tiles(cin, M, (*train_ops._tile_dgrad(cin, M), 0)) == dgrad
+    # the forward list is the inference tuner's for the same op, without the kernels whose record holds a bias, and the static tile
+    infer = [t for t in tuner.conv_tiles(_conv_plan(lib.OP_CONV3X3S2, 1, 1, M, cin, cout), 0) if t[2] not in (lib.CONV3_LDS, lib.CONV3_WREG)]
+    assert fwd[:len(infer)] == infer and len(fwd) - len(infer) <= 1
