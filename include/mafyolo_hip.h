@@ -808,6 +808,19 @@ int maf_coco_accumulate(const int64_t* cat_keys, const int32_t* rank, const uint
  * 9-bit prefix that starts with a code of at most 9 bits, else 0), maxcode int32 [18] (-1: no code of that length), valoff int32 [18]
  * (symbol = huffval[valoff[l] + code]), huffval uint8 [256].  Lanes [group g, group (g + 1)) share one tabset; padding lanes have image -1.
  * maf_jpeg_decode validates the whole HOST copy of the blob (every offset, size and index) before it touches the device.
+ *
+ * Progressive files (SOF2; csrc/jpeg_progressive.hip, rules restated in tests/jpeg_progressive_ref.py) ride in the same blob when the header's
+ * n_scans > 0: behind the quantisation tables follow maf_jpeg_scan_t [n_scans] | maf_jpeg_lane_t [n_slanes] (the "scan lanes") | int32
+ * [n_rounds + 1] round starts.  A progressive image has a maf_jpeg_image_t like any other (its dc_tab / ac_tab unused) and no lane in the
+ * baseline lane table; every scan of it has one row in the scan table (rows sorted by image, then by `round` = the scan's position in its
+ * file) and one scan lane per restart interval OF THAT SCAN, whose `image` field holds the scan-table row and whose first_mcu / n_mcu count
+ * the scan's own MCUs: the frame's MCUs in the interleaved DC scan of all components, single blocks of a bw x bh grid over the component's
+ * own ceil(samples / 8) in a one-component scan (jdinput.c per_scan_setup), addressed inside the padded coefficient planes above.
+ * Scan lanes [rounds[k], rounds[k + 1]) belong to round k: the k-th scan of every image that has one.  The ENTROPY stage launches
+ * jpeg_entropy_kernel over the baseline lanes (if any) and then jpeg_prog_entropy_kernel once per round, in order on the stream: at most
+ * max-scans-per-image launches whatever the batch.  It restates jdphuff.c decode_mcu_DC_first / DC_refine / AC_first / AC_refine; the one
+ * lane that owns a block in a scan reads, modifies and writes its coefficients with ordinary loads and stores.  EOBRUN is lane state, zero at
+ * every restart.  Scan lanes come in groups of `sgroup` sharing one table set, as the baseline lanes do in groups of `group`.
  */
 #define MAF_JPEG_GROUP 64
 #define MAF_JPEG_SCAN_PAD 64
@@ -815,17 +828,21 @@ int maf_coco_accumulate(const int64_t* cat_keys, const int32_t* rank, const uint
 #define MAF_JPEG_ST_BAD_CODE 1      /* no Huffman code matches, or a DC category above 16 */
 #define MAF_JPEG_ST_BAD_INDEX 2     /* an AC run moves past coefficient 63 */
 #define MAF_JPEG_ST_SHORT_SCAN 4    /* the interval's bytes ran out before its MCUs did */
+#define MAF_JPEG_ST_REFINE_PAST_SE 8 /* progressive: an AC run (first pass or refinement) places a coefficient past the scan's Se */
 #define MAF_JPEG_STAGE_ENTROPY 1
 #define MAF_JPEG_STAGE_IDCT 2
 #define MAF_JPEG_STAGE_COLOR 4
 #define MAF_JPEG_STAGE_ALL 7
 typedef struct {
-    int32_t n_images, n_lanes, n_tabsets;
+    int32_t n_images, n_lanes, n_tabsets;    /* n_lanes: the baseline lanes (0 where every file is progressive) */
     int32_t group;                           /* decoding lanes per workgroup, 1 to MAF_JPEG_GROUP; n_lanes is a multiple of it */
     int64_t images_off, lanes_off, huff_off, quant_off, scan_off;   /* byte offsets of the sections in the blob (16-byte aligned) */
     int64_t scan_bytes;                      /* the scans' bytes including the zero padding */
     int64_t total_bytes;                     /* of the blob */
     int64_t coef_elems, plane_bytes, out_bytes;   /* sizes of the three device buffers */
+    int32_t n_scans, n_slanes, n_rounds;     /* progressive: scan-table rows, scan lanes, rounds; all 0 in a call without progressive files */
+    int32_t sgroup;                          /* scan lanes per workgroup, 1 to MAF_JPEG_GROUP; every round's lane count is a multiple of it */
+    int64_t scans_off, slanes_off, rounds_off;
 } maf_jpeg_header_t;
 typedef struct {
     int64_t coef_off;                        /* int16 elements, a multiple of 64 */
@@ -844,7 +861,18 @@ typedef struct {
     int32_t first_mcu, n_mcu;
     int32_t tabset;
 } maf_jpeg_lane_t;
+typedef struct {
+    int32_t image;
+    int32_t round;                           /* the scan's position among its image's scans = the launch it is decoded in */
+    int32_t ncomp;                           /* components in the scan: the image's ncomp (interleaved DC scan) or 1 */
+    int32_t comp[3];                         /* their indices in frame order: 0, 1, 2 when interleaved, else comp[0] */
+    int32_t ss, se, ah, al;                  /* ss == 0 implies se == 0; otherwise ncomp == 1 and ss <= se <= 63; al <= 13; ah == 0 or al + 1 */
+    int32_t dc_tab[3];                       /* DC scans: table 0 or 1 of the lane's set, per scan component */
+    int32_t ac_tab;                          /* AC scans: table 0 or 1 */
+    int32_t bw, bh;                          /* the scan's MCU grid (see above) */
+} maf_jpeg_scan_t;
 int maf_jpeg_struct_sizes(int32_t* header_image_lane);   /* sizeof of the three structs above (binding check) */
+int maf_jpeg_progressive_struct_sizes(int32_t* scan);    /* sizeof(maf_jpeg_scan_t) */
 int maf_jpeg_decode(const void* blob_host, const void* blob_dev, int16_t* coef, uint8_t* planes, uint8_t* out, int32_t* status,
                     int32_t stages, maf_stream_t stream);
 

@@ -3,6 +3,9 @@
 // TrainValDataset.load_image (yolov6/data/datasets.py) and LoadData (yolov6/core/inferer.py).  The rules are restated in tests/jpeg_ref.py
 // (its docstring lists every one with the libjpeg file it comes from); the host side (marker walk, table building) is maf-yolo_amd/jpeg.py.
 //
+// Progressive files (opt-in on the host) take their coefficients from jpeg_prog_entropy_kernel of jpeg_progressive.hip instead, launched by
+// maf_jpeg_decode once per scan round behind jpeg_entropy_kernel; the IDCT and colour kernels below run on both kinds alike.
+//
 // Three kernels, one launch each for the whole batch (include/mafyolo_hip.h describes the blob and the buffers):
 //   jpeg_entropy_kernel   jdhuff.c.  Divergent scalar work: one lane per restart interval, `group` (1 to 64, the host's choice: few lanes per wave while the
 //                         chip has free wave slots, since the lanes of a wave diverge and serialise) decoding lanes per one-wave workgroup, the group's
@@ -18,89 +21,9 @@
 //                         the chroma planes (neighbours clamped to the image's own ceil(w / 2) x ceil(h / 2) samples: the edge rules of
 //                         h2v*_fancy_upsample and the context rows of jdmainct.c), 12 bytes out as three 32-bit stores where aligned.
 #include "maf_common.h"
+#include "jpeg_bits.h"
 
 namespace {
-
-constexpr int TAB_BYTES = MAF_JPEG_HUFF_TABLE_BYTES;
-constexpr int SET_BYTES = 4 * TAB_BYTES;
-constexpr int LOOK_BITS = 9;
-constexpr int OFF_MAXCODE = 2 << LOOK_BITS, OFF_VALOFF = OFF_MAXCODE + 72, OFF_HUFFVAL = OFF_VALOFF + 72;
-static_assert(OFF_HUFFVAL + 256 == TAB_BYTES, "Huffman table layout");
-
-// jutils.c jpeg_natural_order
-__constant__ uint8_t k_zigzag[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
-                                     35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-struct BitReader {
-    const uint8_t* buf;       // the scan buffer
-    int64_t pos, end, last;   // next byte, one past the interval's last byte, the last valid index of the buffer (inside the zero padding)
-    uint64_t acc;             // the low n bits are unread, most significant first
-    int n;
-    int fake;                 // zero bits fed past the end of the interval
-    uint64_t word;            // the aligned 8 bytes of the buffer that hold byte 8 * widx ... (one global load serves 8 byte reads)
-    int64_t widx;
-
-    __device__ __forceinline__ uint32_t byte_at(int64_t i) {
-        i = i < 0 ? 0 : (i > last ? last : i);             // the clamp: whatever the stream says, the index stays inside the scan buffer
-        const int64_t w = i >> 3;
-        if (w != widx) {
-            word = reinterpret_cast<const uint64_t*>(buf)[w];   // the buffer is 16-byte aligned and a multiple of 8 bytes long
-            widx = w;
-        }
-        return (uint32_t)(word >> (8 * (int)(i & 7))) & 0xFFu;
-    }
-
-    __device__ __forceinline__ void fill() {
-        while (n <= 56) {
-            uint32_t b = 0;
-            if (pos < end) {
-                b = byte_at(pos++);
-                if (b == 0xFFu && pos < end) {
-                    if (byte_at(pos) == 0) {
-                        ++pos;                             // 0xFF00: a stuffed data byte 0xFF
-                    } else {                               // a marker inside the interval: its data ends here (jdhuff.c feeds zeros from here on)
-                        pos = end;
-                        b = 0;
-                        fake += 8;
-                    }
-                }
-            } else {
-                fake += 8;
-            }
-            acc = (acc << 8) | b;
-            n += 8;
-        }
-    }
-    __device__ __forceinline__ uint32_t peek16() const { return (uint32_t)(acc >> (n - 16)) & 0xFFFFu; }
-    __device__ __forceinline__ int get(int s) {            // s in [1, 16], n >= s
-        n -= s;
-        return (int)((acc >> n) & ((1u << s) - 1u));
-    }
-};
-
-// one Huffman symbol from table `tab` (LDS); -1: no code matches
-__device__ __forceinline__ int huff_decode(BitReader& br, const uint8_t* tab) {
-    br.fill();
-    const uint32_t c16 = br.peek16();
-    const uint32_t e = reinterpret_cast<const uint16_t*>(tab)[c16 >> (16 - LOOK_BITS)];
-    if (e) {
-        br.n -= (int)(e >> 8);
-        return (int)(e & 0xFFu);
-    }
-    const int* maxcode = reinterpret_cast<const int*>(tab + OFF_MAXCODE);
-    const int* valoff = reinterpret_cast<const int*>(tab + OFF_VALOFF);
-    for (int l = LOOK_BITS + 1; l <= 16; ++l) {
-        const int code = (int)(c16 >> (16 - l));
-        if (code <= maxcode[l]) {
-            br.n -= l;
-            return tab[OFF_HUFFVAL + ((valoff[l] + code) & 255)];
-        }
-    }
-    return -1;
-}
-
-// HUFF_EXTEND of jdhuff.c
-__device__ __forceinline__ int huff_extend(int r, int s) { return r < (1 << (s - 1)) ? r - (1 << s) + 1 : r; }
 
 __global__ __launch_bounds__(MAF_JPEG_GROUP) void jpeg_entropy_kernel(const maf_jpeg_image_t* images, const maf_jpeg_lane_t* lanes, const uint8_t* huff,
                                                                        const uint8_t* scan, int64_t scan_bytes, int group, int16_t* coef, int32_t* status) {
@@ -302,8 +225,6 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const maf_jpeg_image_t*
     }
 }
 
-bool in_blob(int64_t off, int64_t bytes, int64_t total) { return off >= 0 && (off & 15) == 0 && bytes >= 0 && off <= total && bytes <= total - off; }
-
 }  // namespace
 
 extern "C" int maf_jpeg_struct_sizes(int32_t* out) {
@@ -322,7 +243,8 @@ extern "C" int maf_jpeg_decode(const void* blob_host, const void* blob_dev, int1
     const maf_jpeg_header_t hd = *reinterpret_cast<const maf_jpeg_header_t*>(hb);
     const int64_t T = hd.total_bytes;
     MAF_REQUIRE(hd.n_images > 0 && hd.n_images <= 65535, "jpeg_decode: 1 to 65535 images per call");
-    MAF_REQUIRE(hd.group >= 1 && hd.group <= MAF_JPEG_GROUP && hd.n_lanes > 0 && hd.n_lanes % hd.group == 0 && hd.n_tabsets > 0,
+    const bool prog = hd.n_scans != 0 || hd.n_slanes != 0 || hd.n_rounds != 0;      // progressive files in the call (jpeg_progressive.hip): they have no baseline lanes
+    MAF_REQUIRE(hd.group >= 1 && hd.group <= MAF_JPEG_GROUP && (prog ? hd.n_lanes >= 0 : hd.n_lanes > 0) && hd.n_lanes % hd.group == 0 && hd.n_tabsets > 0,
                 "jpeg_decode: the lanes come in whole groups of 1 to MAF_JPEG_GROUP");
     MAF_REQUIRE(T > 0 && T < ((int64_t)1 << 31), "jpeg_decode: blob size out of range");
     MAF_REQUIRE(in_blob(hd.images_off, (int64_t)hd.n_images * (int64_t)sizeof(maf_jpeg_image_t), T) &&
@@ -360,6 +282,10 @@ extern "C" int maf_jpeg_decode(const void* blob_host, const void* blob_dev, int1
         MAF_REQUIRE(l.first_mcu >= 0 && l.n_mcu >= 0 && (int64_t)l.first_mcu + l.n_mcu <= (int64_t)ims[l.image].mcux * ims[l.image].mcuy,
                     "jpeg_decode: a lane's MCUs lie outside its image");
     }
+    if (prog) {
+        const int rc = maf_jpeg_progressive_validate(hb, hd);
+        if (rc) return rc;
+    }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const uint8_t* db = static_cast<const uint8_t*>(blob_dev);
     const maf_jpeg_image_t* d_ims = reinterpret_cast<const maf_jpeg_image_t*>(db + hd.images_off);
@@ -368,10 +294,16 @@ extern "C" int maf_jpeg_decode(const void* blob_host, const void* blob_dev, int1
         if (rc) return rc;
         rc = maf_check_hip(hipMemsetAsync(status, 0, (size_t)hd.n_images * sizeof(int32_t), s), "jpeg_decode memset");
         if (rc) return rc;
-        hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(hd.n_lanes / hd.group), dim3(MAF_JPEG_GROUP), 0, s, d_ims,
-                           reinterpret_cast<const maf_jpeg_lane_t*>(db + hd.lanes_off), db + hd.huff_off, db + hd.scan_off, hd.scan_bytes, hd.group, coef, status);
-        rc = maf_check_hip(hipGetLastError(), "jpeg_entropy launch");
-        if (rc) return rc;
+        if (hd.n_lanes > 0) {
+            hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(hd.n_lanes / hd.group), dim3(MAF_JPEG_GROUP), 0, s, d_ims,
+                               reinterpret_cast<const maf_jpeg_lane_t*>(db + hd.lanes_off), db + hd.huff_off, db + hd.scan_off, hd.scan_bytes, hd.group, coef, status);
+            rc = maf_check_hip(hipGetLastError(), "jpeg_entropy launch");
+            if (rc) return rc;
+        }
+        if (prog) {
+            rc = maf_jpeg_progressive_launch(hb, db, hd, coef, status, s);
+            if (rc) return rc;
+        }
     }
     if (stages & MAF_JPEG_STAGE_IDCT) {
         hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + 255) / 256), hd.n_images), dim3(256), 0, s, d_ims,

@@ -1,4 +1,5 @@
-"""File bytes in, frames out, on the device: baseline JPEG decoding that equals libjpeg's defaults (what cv2.imread returns) bit for bit.
+"""File bytes in, frames out, on the device: JPEG decoding (baseline, and progressive on request) that equals libjpeg's defaults (what
+cv2.imread returns) bit for bit.
 
 The stage in front of letterbox.py / augment.py that the reference runs on the host, one file at a time, through cv2.imread
 (yolov6/data/datasets.py load_image, LoadData of yolov6/core/inferer.py):
@@ -11,6 +12,11 @@ The stage in front of letterbox.py / augment.py that the reference runs on the h
 Supported: baseline sequential DCT (SOF0), 8 bit, Huffman, one interleaved scan, 1 component or 3 (Y 1x1, 2x1 or 2x2 with 1x1 chroma).
 The pixels follow libjpeg's JDCT_ISLOW + fancy upsampling + jdcolor.c tables as restated in tests/jpeg_ref.py.  cv2.imread also rotates by
 the EXIF orientation; this decoder does not, so such a file raises JpegUnsupported unless ignore_orientation=True.  No CPU fallback.
+Opt-in, progressive=True on parse / supported / decode: progressive DCT (SOF2, 8 bit, Huffman) with the same components and samplings, every
+scan of the file walked and validated as jdphuff.c start_pass_phuff_decoder does (JpegInfo.scans: one JpegScan per SOS with the Huffman
+tables and the restart interval in force there); csrc/jpeg_progressive.hip decodes scan k of every file of the call in launch k, the IDCT
+and colour kernels run unchanged on the finished coefficients (rules restated in tests/jpeg_progressive_ref.py).  A progression that leaves
+a coefficient unfinished (libjpeg would smooth it) or that libjpeg warns about raises JpegUnsupported.  Without the flag nothing changes.
 """
 import os
 import struct
@@ -27,18 +33,23 @@ class JpegUnsupported(MafError):
 
 
 JpegComponent = namedtuple("JpegComponent", "id h v tq td ta")
-JpegInfo = namedtuple("JpegInfo", "width height precision components qtables huffman restart_interval scan orientation adobe_transform")
+JpegInfo = namedtuple("JpegInfo", "width height precision components qtables huffman restart_interval scan orientation adobe_transform scans",
+                      defaults=(None,))
+JpegScan = namedtuple("JpegScan", "components ss se ah al td ta restart_interval huffman range")
 # qtables: {id: uint16 [64] in natural (row-major) order}; huffman: {(class, id): (bits uint8 [16], values uint8 [n])}, class 0 = DC, 1 = AC;
 # scan: (first byte, one past the last byte) of the entropy-coded segment, RST markers included; orientation: the EXIF tag or None
+# scans: None for a baseline file; for a progressive one (parse(..., progressive=True)) one JpegScan per SOS in file order: components = indices
+# into JpegInfo.components, ss / se / ah / al, td / ta = the DC / AC table selector per scan component, and the restart interval, the Huffman
+# tables and the byte range of THAT scan (DHT and DRI may change between scans); JpegInfo.scan then spans first scan .. last scan
 
 # jpeg_natural_order of jutils.c: zigzag position -> row-major position
 ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
                    35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63],
                   np.int64)
 
-STATUS_BAD_CODE, STATUS_BAD_INDEX, STATUS_SHORT_SCAN = 1, 2, 4      # MAF_JPEG_ST_*: bits of a per-image status word
+STATUS_BAD_CODE, STATUS_BAD_INDEX, STATUS_SHORT_SCAN, STATUS_REFINE_PAST_SE = 1, 2, 4, 8      # MAF_JPEG_ST_*: bits of a per-image status word
 _STATUS_TEXT = ((STATUS_BAD_CODE, "an invalid Huffman code"), (STATUS_BAD_INDEX, "a coefficient index past 63"),
-                (STATUS_SHORT_SCAN, "a scan that ends early"))
+                (STATUS_SHORT_SCAN, "a scan that ends early"), (STATUS_REFINE_PAST_SE, "a refinement run that moves past the end of its band"))
 
 _SOF_NAMES = {0xC1: "extended sequential DCT (SOF1)", 0xC2: "progressive DCT (SOF2)", 0xC3: "lossless (SOF3)",
               0xC5: "differential sequential DCT (SOF5)", 0xC6: "differential progressive DCT (SOF6)", 0xC7: "differential lossless (SOF7)",
@@ -80,8 +91,208 @@ def _exif_orientation(seg):
     return None
 
 
-def parse(data):
-    """Walk the markers of one JPEG file (bytes-like or a path) -> JpegInfo.  Host only."""
+def _read_dqt(seg, short, qt):
+    """The tables of one DQT segment into qt (natural order)."""
+    q = 0
+    while q < len(seg):
+        pq, tq = seg[q] >> 4, seg[q] & 15
+        if pq != 0:
+            raise JpegUnsupported("jpeg: 16-bit quantisation tables are not supported")
+        if short or q + 65 > len(seg):
+            raise MafError("jpeg: a DQT segment runs past the end of the file")
+        t = np.zeros(64, np.uint16)
+        t[ZIGZAG] = np.frombuffer(seg, np.uint8, 64, q + 1)
+        qt[tq] = t
+        q += 65
+
+
+def _read_dht(seg, short, huff):
+    """The tables of one DHT segment into huff."""
+    q = 0
+    if short:
+        raise MafError("jpeg: a DHT segment runs past the end of the file")
+    while q < len(seg):
+        if q + 17 > len(seg):
+            raise MafError("jpeg: a DHT segment is cut short")
+        tc, th = seg[q] >> 4, seg[q] & 15
+        bits = np.frombuffer(seg, np.uint8, 16, q + 1).copy()
+        cnt = int(bits.sum())
+        if tc > 1 or cnt > 256 or q + 17 + cnt > len(seg):
+            raise MafError("jpeg: a malformed DHT segment")
+        huff[(tc, th)] = (bits, np.frombuffer(seg, np.uint8, cnt, q + 17).copy())
+        q += 17 + cnt
+
+
+def _check_frame(comps, adobe):
+    """The sampling and colour-space limits: 1 component (its factors are irrelevant in a non-interleaved scan) or Y 1x1 / 2x1 / 2x2 with 1x1 chroma."""
+    if len(comps) == 3:
+        y, cb, cr = comps
+        if (cb.h, cb.v, cr.h, cr.v) != (1, 1, 1, 1) or (y.h, y.v) not in ((1, 1), (2, 1), (2, 2)):
+            raise JpegUnsupported("jpeg: sampling %s is not supported (Y 1x1, 2x1 or 2x2 with 1x1 chroma)"
+                                  % ", ".join("%dx%d" % (c.h, c.v) for c in comps))
+        if adobe == 0 or bytes(c.id for c in comps) == b"RGB":
+            raise JpegUnsupported("jpeg: an RGB (untransformed) colour space is not supported (YCbCr only)")
+
+
+def _parse_progressive(d):
+    """parse() for a progressive file (SOF2): every scan walked and validated as jdphuff.c start_pass_phuff_decoder does, with libjpeg's
+    coef_bits bookkeeping (per component and coefficient: the Al it has reached, -1 = never sent).  What libjpeg only warns about
+    (JWRN_BOGUS_PROGRESSION) and a progression that is incomplete at EOI (jdcoefct.c smoothing_ok would smooth) raise JpegUnsupported."""
+    n = len(d)
+    a = np.frombuffer(d, np.uint8)
+    nxt = a[1:]
+    # every 0xFF that starts a marker other than RSTn (not a stuffed 0xFF00, not a fill 0xFF): where an entropy-coded segment can end
+    marks = np.flatnonzero((a[:-1] == 0xFF) & (nxt != 0) & (nxt != 0xFF) & ((nxt < 0xD0) | (nxt > 0xD7)))
+    qt, huff = {}, {}
+    frame = None
+    restart = 0
+    orientation = adobe = None
+    comps, scans, coef_bits = None, [], None
+    p = 2
+    while True:
+        if p + 2 > n:
+            raise MafError("jpeg: the file ends before a scan (no SOS marker)" if not scans else "jpeg: no EOI marker after the scan")
+        if d[p] != 0xFF:
+            raise MafError("jpeg: expected a marker at byte %d" % p)
+        m = d[p + 1]
+        if m == 0xFF:
+            p += 1
+            continue
+        p += 2
+        if m == 0xD9:
+            if not scans:
+                raise MafError("jpeg: EOI before any scan")
+            break
+        if m == 0x01 or 0xD0 <= m <= 0xD7:
+            continue
+        if p + 2 > n:
+            raise MafError("jpeg: a segment length runs past the end of the file")
+        L = (d[p] << 8) | d[p + 1]
+        seg = d[p + 2:p + L]
+        short = L < 2 or p + L > n
+        if m == 0xCC:
+            raise JpegUnsupported("jpeg: arithmetic coding (DAC marker) is not supported")
+        if m == 0xC0 or m in _SOF_NAMES:
+            if frame is not None:
+                raise MafError("jpeg: a second SOF marker")
+            if m != 0xC2:
+                raise MafError("jpeg: a frame header other than the SOF2 the file began with")      # parse() routes here on the first SOF only
+            if len(seg) < 6:
+                raise MafError("jpeg: the SOF2 segment runs past the end of the file")
+            prec, h, w, nf = seg[0], (seg[1] << 8) | seg[2], (seg[3] << 8) | seg[4], seg[5]
+            if prec != 8:
+                raise JpegUnsupported("jpeg: %d-bit samples are not supported (8-bit only)" % prec)
+            if nf not in (1, 3):
+                raise JpegUnsupported("jpeg: %d components are not supported (1 or 3)" % nf)
+            if short or len(seg) < 6 + 3 * nf:
+                raise MafError("jpeg: the SOF2 segment runs past the end of the file")
+            if h == 0 or w == 0:
+                raise JpegUnsupported("jpeg: a frame height of 0 (DNL marker) is not supported" if w else "jpeg: zero width")
+            frame = (w, h)
+            comps = tuple(JpegComponent(seg[6 + 3 * i], seg[7 + 3 * i] >> 4, seg[7 + 3 * i] & 15, seg[8 + 3 * i], 0, 0) for i in range(nf))
+            _check_frame(comps, None)
+            coef_bits = [[-1] * 64 for _ in comps]
+        elif m == 0xDB:
+            if scans:
+                raise JpegUnsupported("jpeg: a DQT segment after the first SOS of a progressive file is not supported")
+            _read_dqt(seg, short, qt)
+        elif m == 0xC4:
+            _read_dht(seg, short, huff)
+        elif m == 0xDD:
+            if short or len(seg) < 2:
+                raise MafError("jpeg: the DRI segment runs past the end of the file")
+            restart = (seg[0] << 8) | seg[1]
+        elif m == 0xDC:
+            raise JpegUnsupported("jpeg: a DNL marker is not supported")
+        elif m == 0xE1:
+            if short:
+                raise MafError("jpeg: an APP1 segment runs past the end of the file")
+            o = _exif_orientation(seg)
+            orientation = o if o is not None else orientation
+        elif m == 0xEE:
+            if short:
+                raise MafError("jpeg: an APP14 segment runs past the end of the file")
+            if len(seg) >= 12 and seg[:5] == b"Adobe":
+                adobe = seg[11]
+        elif m == 0xDA:
+            k = len(scans)
+            if frame is None:
+                raise MafError("jpeg: SOS before SOF")
+            if len(seg) < 1:
+                raise MafError("jpeg: the SOS segment runs past the end of the file")
+            ns = seg[0]
+            if ns < 1 or ns > 4:
+                raise MafError("jpeg: scan %d names %d components" % (k, ns))
+            if short or len(seg) < 4 + 2 * ns:
+                raise MafError("jpeg: the SOS segment runs past the end of the file")
+            ids = [c.id for c in comps]
+            idx, td, ta = [], [], []
+            for i in range(ns):
+                if seg[1 + 2 * i] not in ids:
+                    raise MafError("jpeg: scan %d names component id %d, which the frame does not have" % (k, seg[1 + 2 * i]))
+                idx.append(ids.index(seg[1 + 2 * i]))
+                td.append(seg[2 + 2 * i] >> 4)
+                ta.append(seg[2 + 2 * i] & 15)
+            ss, se, ah, al = seg[1 + 2 * ns], seg[2 + 2 * ns], seg[3 + 2 * ns] >> 4, seg[3 + 2 * ns] & 15
+            what = "scan %d (components %s, Ss %d, Se %d, Ah %d, Al %d)" % (k, idx, ss, se, ah, al)
+            # jdphuff.c start_pass_phuff_decoder (JERR_BAD_PROGRESSION there)
+            if ss == 0:
+                if se != 0:
+                    raise JpegUnsupported("jpeg: %s: a progressive scan that starts at the DC coefficient must end there (Ss 0 needs Se 0)" % what)
+            elif ns != 1:
+                raise JpegUnsupported("jpeg: %s: a progressive AC scan takes one component" % what)
+            elif se < ss or se > 63:
+                raise JpegUnsupported("jpeg: %s: a progressive AC band needs Ss <= Se <= 63" % what)
+            if ah != 0 and al != ah - 1:
+                raise JpegUnsupported("jpeg: %s: a progressive refinement scan needs Al = Ah - 1" % what)
+            if al > 13:
+                raise JpegUnsupported("jpeg: %s: a progressive scan with Al above 13" % what)
+            if ns > 1 and idx != list(range(len(comps))):
+                raise JpegUnsupported("jpeg: %s: a progressive DC scan of some of the components, or in another order, is not supported "
+                                      "(all of them in frame order, or one)" % what)
+            for j, c in enumerate(idx):                     # the coef_bits loop (JWRN_BOGUS_PROGRESSION there)
+                bits = coef_bits[c]
+                if ss != 0 and bits[0] < 0:
+                    raise JpegUnsupported("jpeg: %s: a bogus progression, an AC scan before the component's first DC scan" % what)
+                for ci in range(ss, se + 1):
+                    if ah != max(bits[ci], 0):
+                        raise JpegUnsupported("jpeg: %s: a bogus progression, Ah %d where coefficient %d stands at %s" %
+                                              (what, ah, ci, "bit %d" % bits[ci] if bits[ci] >= 0 else "never sent"))
+                    bits[ci] = al
+                sel = td[j] if ss == 0 else ta[j]
+                if ss == 0 and ah != 0:
+                    continue                                # a DC refinement scan reads raw bits: no table
+                if sel > 1:
+                    raise JpegUnsupported("jpeg: Huffman table selectors above 1 are not supported")
+                if (0 if ss == 0 else 1, sel) not in huff:
+                    raise MafError("jpeg: Huffman table %s %d of scan %d is missing" % ("DC" if ss == 0 else "AC", sel, k))
+            p += L
+            at = int(np.searchsorted(marks, p))
+            if at >= marks.size:
+                raise MafError("jpeg: no EOI marker after the scan")
+            end = int(marks[at])
+            scans.append(JpegScan(tuple(idx), ss, se, ah, al, tuple(td), tuple(ta), restart, dict(huff), (p, end)))
+            p = end
+            continue
+        elif short:
+            raise MafError("jpeg: a segment (marker 0xFF%02X) runs past the end of the file" % m)
+        p += L
+    _check_frame(comps, adobe)
+    for c in comps:
+        if c.tq not in qt:
+            raise MafError("jpeg: quantisation table %d is missing" % c.tq)
+    for c, bits in enumerate(coef_bits):
+        left = [ci for ci in range(64) if bits[ci] != 0]
+        if left:
+            raise JpegUnsupported("jpeg: an incomplete progression is not supported (libjpeg would smooth the blocks): after the %d scans of the "
+                                  "file, coefficient %d of component %d %s" % (len(scans), left[0], c, "was never sent" if bits[left[0]] < 0
+                                                                               else "stands at bit %d" % bits[left[0]]))
+    return JpegInfo(frame[0], frame[1], 8, comps, qt, dict(huff), scans[0].restart_interval, (scans[0].range[0], scans[-1].range[1]), orientation,
+                    adobe, tuple(scans))
+
+
+def parse(data, progressive=False):
+    """Walk the markers of one JPEG file (bytes-like or a path) -> JpegInfo.  Host only.  progressive=True also takes SOF2 files (JpegInfo.scans)."""
     d = _bytes(data)
     n = len(d)
     if n < 4 or d[0] != 0xFF or d[1] != 0xD8:
@@ -113,8 +324,11 @@ def parse(data):
         short = L < 2 or p + L > n                          # judged after the fields that name an unsupported kind have been read
         if m == 0xCC:
             raise JpegUnsupported("jpeg: arithmetic coding (DAC marker) is not supported")
+        if m == 0xC2 and progressive and frame is None:
+            return _parse_progressive(d)
         if m in _SOF_NAMES:
-            raise JpegUnsupported("jpeg: %s is not supported (baseline SOF0 only)" % _SOF_NAMES[m])
+            raise JpegUnsupported("jpeg: %s is not supported (baseline SOF0 only)" % _SOF_NAMES[m] if not progressive else
+                                  "jpeg: %s is not supported (baseline SOF0 and progressive SOF2 only)" % _SOF_NAMES[m])
         if m == 0xC0:
             if len(seg) < 6:
                 raise MafError("jpeg: the SOF0 segment runs past the end of the file")
@@ -131,31 +345,9 @@ def parse(data):
                 raise JpegUnsupported("jpeg: a frame height of 0 (DNL marker) is not supported" if w else "jpeg: zero width")
             frame = (w, h, [(seg[6 + 3 * i], seg[7 + 3 * i] >> 4, seg[7 + 3 * i] & 15, seg[8 + 3 * i]) for i in range(nf)])
         elif m == 0xDB:
-            q = 0
-            while q < len(seg):
-                pq, tq = seg[q] >> 4, seg[q] & 15
-                if pq != 0:
-                    raise JpegUnsupported("jpeg: 16-bit quantisation tables are not supported")
-                if short or q + 65 > len(seg):
-                    raise MafError("jpeg: a DQT segment runs past the end of the file")
-                t = np.zeros(64, np.uint16)
-                t[ZIGZAG] = np.frombuffer(seg, np.uint8, 64, q + 1)
-                qt[tq] = t
-                q += 65
+            _read_dqt(seg, short, qt)
         elif m == 0xC4:
-            q = 0
-            if short:
-                raise MafError("jpeg: a DHT segment runs past the end of the file")
-            while q < len(seg):
-                if q + 17 > len(seg):
-                    raise MafError("jpeg: a DHT segment is cut short")
-                tc, th = seg[q] >> 4, seg[q] & 15
-                bits = np.frombuffer(seg, np.uint8, 16, q + 1).copy()
-                cnt = int(bits.sum())
-                if tc > 1 or cnt > 256 or q + 17 + cnt > len(seg):
-                    raise MafError("jpeg: a malformed DHT segment")
-                huff[(tc, th)] = (bits, np.frombuffer(seg, np.uint8, cnt, q + 17).copy())
-                q += 17 + cnt
+            _read_dht(seg, short, huff)
         elif m == 0xDD:
             if short or len(seg) < 2:
                 raise MafError("jpeg: the DRI segment runs past the end of the file")
@@ -194,14 +386,7 @@ def parse(data):
             raise MafError("jpeg: a segment (marker 0xFF%02X) runs past the end of the file" % m)
         p += L
     w, h, _ = frame
-    # sampling: 1 component (its factors are irrelevant in a non-interleaved scan) or Y 1x1 / 2x1 / 2x2 with 1x1 chroma
-    if len(comps) == 3:
-        y, cb, cr = comps
-        if (cb.h, cb.v, cr.h, cr.v) != (1, 1, 1, 1) or (y.h, y.v) not in ((1, 1), (2, 1), (2, 2)):
-            raise JpegUnsupported("jpeg: sampling %s is not supported (Y 1x1, 2x1 or 2x2 with 1x1 chroma)"
-                                  % ", ".join("%dx%d" % (c.h, c.v) for c in comps))
-        if adobe == 0 or bytes(c.id for c in comps) == b"RGB":
-            raise JpegUnsupported("jpeg: an RGB (untransformed) colour space is not supported (YCbCr only)")
+    _check_frame(comps, adobe)
     for c in comps:
         if c.tq not in qt:
             raise MafError("jpeg: quantisation table %d is missing" % c.tq)
@@ -226,10 +411,11 @@ def parse(data):
     return JpegInfo(w, h, 8, tuple(comps), qt, huff, restart, (p, end), orientation, adobe)
 
 
-def supported(data):
-    """True where decode() takes this file: a baseline JPEG of the supported set without an EXIF rotation."""
+def supported(data, progressive=False):
+    """True where decode() takes this file: a baseline JPEG (with progressive=True also a progressive one) of the supported set without an
+    EXIF rotation."""
     try:
-        return parse(data).orientation in (None, 1)
+        return parse(data, progressive).orientation in (None, 1)
     except MafError:
         return False
 
@@ -248,7 +434,10 @@ IMAGE_DT = np.dtype([("coef_off", "<i8"), ("plane_off", "<i8"), ("out_off", "<i8
 LANE_DT = np.dtype([("begin", "<i8"), ("end", "<i8"), ("image", "<i4"), ("first_mcu", "<i4"), ("n_mcu", "<i4"), ("tabset", "<i4")])   # maf_jpeg_lane_t
 HEADER_DT = np.dtype([("n_images", "<i4"), ("n_lanes", "<i4"), ("n_tabsets", "<i4"), ("group", "<i4"), ("images_off", "<i8"), ("lanes_off", "<i8"),
                       ("huff_off", "<i8"), ("quant_off", "<i8"), ("scan_off", "<i8"), ("scan_bytes", "<i8"), ("total_bytes", "<i8"),
-                      ("coef_elems", "<i8"), ("plane_bytes", "<i8"), ("out_bytes", "<i8")])               # maf_jpeg_header_t
+                      ("coef_elems", "<i8"), ("plane_bytes", "<i8"), ("out_bytes", "<i8"), ("n_scans", "<i4"), ("n_slanes", "<i4"), ("n_rounds", "<i4"),
+                      ("sgroup", "<i4"), ("scans_off", "<i8"), ("slanes_off", "<i8"), ("rounds_off", "<i8")])  # maf_jpeg_header_t
+SCAN_DT = np.dtype([("image", "<i4"), ("round", "<i4"), ("ncomp", "<i4"), ("comp", "<i4", 3), ("ss", "<i4"), ("se", "<i4"), ("ah", "<i4"), ("al", "<i4"),
+                    ("dc_tab", "<i4", 3), ("ac_tab", "<i4"), ("bw", "<i4"), ("bh", "<i4")])               # maf_jpeg_scan_t
 SCAN_PAD = 64                 # zero bytes the host appends to the scan buffer (the bit reader's clamp lands in them)
 STAGE_ENTROPY, STAGE_IDCT, STAGE_COLOR, STAGE_ALL = 1, 2, 4, 7
 
@@ -306,19 +495,51 @@ def geometry(info):
     return nc, hs, vs, mcux, mcuy, blocks
 
 
+def scan_geometry(info, scan):
+    """(blocks per row, block rows) of the MCU grid of one scan of a progressive file: the frame's MCU grid for the interleaved (DC) scan of
+    all components; for a one-component scan ceil(comp_w / 8) x ceil(comp_h / 8) blocks over the component's OWN sample dimensions (an MCU is
+    one block there: jdinput.c per_scan_setup), which is smaller than the padded grid the coefficient buffer is addressed by."""
+    nc, hs, vs, mcux, mcuy, _ = geometry(info)
+    if len(scan.components) > 1:
+        return mcux, mcuy
+    ch, cv = (hs, vs) if scan.components[0] == 0 else (1, 1)
+    cw, chh = -(-info.width * ch // hs), -(-info.height * cv // vs)
+    return -(-cw // 8), -(-chh // 8)
+
+
+def _group_of(n_lanes):
+    """Lanes per one-wave workgroup: 1 while the chip has free wave slots, doubling (up to MAX_GROUP) beyond."""
+    group = 1
+    while group < MAX_GROUP and n_lanes > WAVE_SLOTS * group:
+        group *= 2
+    return group
+
+
 def _align(x, a=16):
     return (x + a - 1) // a * a
 
 
 def build_blob(datas, infos):
     """Everything the device needs for one call, in one byte array: header | image table | lane table | Huffman table sets | quantisation
-    tables | the scans' bytes + SCAN_PAD zeros.  -> (blob uint8 array, header record, image table)."""
+    tables | with progressive files: scan table | scan lanes | round starts | the scans' bytes + SCAN_PAD zeros.
+    -> (header record, image table, lane table, Huffman table sets, quantisation tables, each file's offset in the scan bytes,
+    (scan table, scan lanes, round starts) or None)."""
     B = len(infos)
     images = np.zeros(B, IMAGE_DT)
     quant = np.zeros((B, 3, 64), np.uint16)
     tabsets, set_bytes, groups = {}, [], []
     coef = plane = outb = scanb = 0
     scan_at = []
+    scan_rows, rounds = [], []             # progressive files: the scan table; rounds[k][table set] = lanes of the k-th scan of every file that has one
+
+    def tabset_of(key):
+        if key not in tabsets:
+            tabsets[key] = len(set_bytes)
+            set_bytes.append(np.concatenate([np.zeros(HUFF_TABLE_BYTES, np.uint8) if t is None else
+                                             huff_device_table(np.frombuffer(t[0], np.uint8), np.frombuffer(t[1], np.uint8)) for t in key]))
+            groups.append([])
+        return tabsets[key]
+
     for i, (d, info) in enumerate(zip(datas, infos)):
         nc, hs, vs, mcux, mcuy, blocks = geometry(info)
         im = images[i]
@@ -330,28 +551,47 @@ def build_blob(datas, infos):
         coef += 64 * sum(blocks)
         plane += 64 * sum(blocks)
         outb += _align(3 * info.width * info.height)
-        key = tuple(None if k not in info.huffman else (info.huffman[k][0].tobytes(), info.huffman[k][1].tobytes())
-                    for k in ((0, 0), (0, 1), (1, 0), (1, 1)))
-        if key not in tabsets:
-            tabsets[key] = len(set_bytes)
-            set_bytes.append(np.concatenate([np.zeros(HUFF_TABLE_BYTES, np.uint8) if t is None else
-                                             huff_device_table(np.frombuffer(t[0], np.uint8), np.frombuffer(t[1], np.uint8)) for t in key]))
-            groups.append([])
-        ts = tabsets[key]
+        s, e = info.scan
+        if info.scans is not None:                           # progressive: one scan-table row and one lane per restart interval of every scan
+            for k, sc in enumerate(info.scans):
+                dc = sc.ss == 0
+                used = set() if dc and sc.ah else {(0 if dc else 1, t) for t in (sc.td if dc else sc.ta)}
+                ts = tabset_of(tuple((sc.huffman[q][0].tobytes(), sc.huffman[q][1].tobytes()) if q in used else None
+                                     for q in ((0, 0), (0, 1), (1, 0), (1, 1))))
+                bw, bh = scan_geometry(info, sc)
+                total = bw * bh
+                ri = sc.restart_interval if sc.restart_interval else total
+                nl = -(-total // ri)
+                while len(rounds) <= k:
+                    rounds.append({})
+                row = rounds[k].setdefault(ts, [])
+                for j, (b0, b1) in enumerate(_restart_ranges(d, sc.range, nl)):
+                    row.append((scanb + b0 - s, scanb + b1 - s, len(scan_rows), j * ri, min(ri, total - j * ri), ts))
+                scan_rows.append((i, k, len(sc.components), tuple(sc.components) + (0,) * (3 - len(sc.components)), sc.ss, sc.se, sc.ah, sc.al,
+                                  tuple(sc.td) + (0,) * (3 - len(sc.td)) if dc else (0, 0, 0), 0 if dc else sc.ta[0], bw, bh))
+            scan_at.append(scanb)
+            scanb += e - s
+            continue
+        ts = tabset_of(tuple(None if k not in info.huffman else (info.huffman[k][0].tobytes(), info.huffman[k][1].tobytes())
+                             for k in ((0, 0), (0, 1), (1, 0), (1, 1))))
         total = mcux * mcuy
         ri = info.restart_interval if info.restart_interval else total
         nl = -(-total // ri)
-        s, e = info.scan
         for k, (b0, b1) in enumerate(_restart_ranges(d, info.scan, nl)):
             groups[ts].append((scanb + b0 - s, scanb + b1 - s, i, k * ri, min(ri, total - k * ri), ts))
         scan_at.append(scanb)
         scanb += e - s
-    rows, group = [], 1
-    while group < MAX_GROUP and sum(len(g) for g in groups) > WAVE_SLOTS * group:
-        group *= 2
+    rows, group = [], _group_of(sum(len(g) for g in groups))
     for ts, g in enumerate(groups):                          # lanes of one workgroup share a table set: pad every set's lanes to whole groups
         rows += g + [(0, 0, -1, 0, 0, ts)] * (-len(g) % group)
     lanes = np.array(rows, LANE_DT)
+    srows, starts = [], [0]                                  # the scan lanes, round after round, each round's table sets padded to whole groups
+    sgroup = _group_of(max((sum(len(g) for g in r.values()) for r in rounds), default=0))
+    for r in rounds:
+        for ts, g in r.items():
+            srows += g + [(0, 0, -1, 0, 0, ts)] * (-len(g) % sgroup)
+        starts.append(len(srows))
+    scans, slanes, round_at = np.array(scan_rows, SCAN_DT), np.array(srows, LANE_DT), np.array(starts, np.int32)
     hdr = np.zeros(1, HEADER_DT)[0]
     off = _align(HEADER_DT.itemsize)
     hdr["n_images"], hdr["n_lanes"], hdr["n_tabsets"], hdr["group"] = B, len(lanes), len(set_bytes), group
@@ -363,19 +603,30 @@ def build_blob(datas, infos):
     off = _align(off + HUFF_SET_BYTES * len(set_bytes))
     hdr["quant_off"] = off
     off = _align(off + quant.nbytes)
+    if scan_rows:                                            # a call without progressive files has none of these sections
+        hdr["n_scans"], hdr["n_slanes"], hdr["n_rounds"], hdr["sgroup"] = len(scans), len(slanes), len(rounds), sgroup
+        hdr["scans_off"] = off
+        off = _align(off + scans.nbytes)
+        hdr["slanes_off"] = off
+        off = _align(off + slanes.nbytes)
+        hdr["rounds_off"] = off
+        off = _align(off + round_at.nbytes)
     hdr["scan_off"] = off
     hdr["scan_bytes"] = _align(scanb + SCAN_PAD)           # a multiple of 8: the bit reader loads aligned 8-byte words
     hdr["total_bytes"] = off + _align(scanb + SCAN_PAD)
     hdr["coef_elems"], hdr["plane_bytes"], hdr["out_bytes"] = coef, plane, outb
     if hdr["total_bytes"] >= 2 ** 31 or B > 65535:
         raise MafError("jpeg: decode() takes up to 65535 files and 2 GiB of file bytes per call")
-    return hdr, images, lanes, np.concatenate(set_bytes), quant, scan_at
+    return hdr, images, lanes, np.concatenate(set_bytes), quant, scan_at, ((scans, slanes, round_at) if scan_rows else None)
 
 
-def fill_blob(buf, hdr, images, lanes, huff, quant, datas, infos, scan_at):
+def fill_blob(buf, hdr, images, lanes, huff, quant, datas, infos, scan_at, prog=None):
     """Write the sections of build_blob into `buf` (a uint8 array of hdr.total_bytes: the pinned staging buffer)."""
     buf[:HEADER_DT.itemsize] = np.frombuffer(hdr.tobytes(), np.uint8)
-    for name, arr in (("images_off", images), ("lanes_off", lanes), ("huff_off", huff), ("quant_off", quant)):
+    sections = [("images_off", images), ("lanes_off", lanes), ("huff_off", huff), ("quant_off", quant)]
+    if prog is not None:
+        sections += zip(("scans_off", "slanes_off", "rounds_off"), prog)
+    for name, arr in sections:
         o = int(hdr[name])
         buf[o:o + arr.nbytes] = arr.reshape(-1).view(np.uint8)
     so = int(hdr["scan_off"])
@@ -396,9 +647,11 @@ def _library():
         import ctypes
         sizes = (ctypes.c_int32 * 3)()
         lib.check(L.maf_jpeg_struct_sizes(sizes))
-        if list(sizes) != [HEADER_DT.itemsize, IMAGE_DT.itemsize, LANE_DT.itemsize]:
-            raise MafError("libmafyolo_hip.so was built for maf_jpeg_* structs of %s bytes, this binding declares %s: rebuild"
-                           % (list(sizes), [HEADER_DT.itemsize, IMAGE_DT.itemsize, LANE_DT.itemsize]))
+        sizes_p = (ctypes.c_int32 * 1)()
+        lib.check(L.maf_jpeg_progressive_struct_sizes(sizes_p))
+        have, want = list(sizes) + list(sizes_p), [HEADER_DT.itemsize, IMAGE_DT.itemsize, LANE_DT.itemsize, SCAN_DT.itemsize]
+        if have != want:
+            raise MafError("libmafyolo_hip.so was built for maf_jpeg_* structs of %s bytes, this binding declares %s: rebuild" % (have, want))
         _lib_checked = True
     return L
 
@@ -411,13 +664,15 @@ def status_text(word):
     return ", ".join(t for bit, t in _STATUS_TEXT if word & bit) or "status 0x%x" % word
 
 
-def decode(files, device=None, stream=None, ignore_orientation=False, check=True, stages=STAGE_ALL, taps=None):
-    """Decode a list of baseline JPEG files (bytes-like objects or paths; mixed sizes and samplings welcome) on the device.
+def decode(files, device=None, stream=None, ignore_orientation=False, check=True, stages=STAGE_ALL, taps=None, progressive=False):
+    """Decode a list of baseline JPEG files (bytes-like objects or paths; mixed sizes and samplings welcome) on the device; with
+    progressive=True the list may also hold progressive files (scan k of every file of the call is one launch: jpeg_prog_entropy_kernel).
     -> a list of uint8 [h_i, w_i, 3] BGR CUDA tensors (views of one allocation), what cv2.imread returns for each file; they go into
     letterbox / eval_batch / detect_frames / train_batch as they are.  With check=True (the default) the per-image status words are read
     once after the launches (the call's one synchronisation) and a fault raises MafError naming the file; check=False returns
     (frames, status int32 [B]) without synchronising.  `stream`: a torch.cuda.Stream to work on (default: the current one).
-    `taps`: a dict that receives the intermediate buffers (coefficients, planes, the image table) — tests and the probe."""
+    `taps`: a dict that receives the intermediate buffers (coefficients, planes, the image table; "progressive": the scan table, the scan
+    lanes and the round starts, or None) — tests and the probe."""
     import torch
     files = list(files)
     if not files:
@@ -431,7 +686,7 @@ def decode(files, device=None, stream=None, ignore_orientation=False, check=True
     for i, f in enumerate(files):
         d = _bytes(f)
         try:
-            info = parse(d)
+            info = parse(d, progressive)
         except MafError as e:
             raise type(e)("%s: %s" % (_name(f, i), e)) from None
         if info.orientation not in (None, 1) and not ignore_orientation:
@@ -439,13 +694,13 @@ def decode(files, device=None, stream=None, ignore_orientation=False, check=True
                                   "(pass ignore_orientation=True to take the stored pixels)" % (_name(f, i), info.orientation))
         datas.append(d)
         infos.append(info)
-    hdr, images, lanes, huff, quant, scan_at = build_blob(datas, infos)
+    hdr, images, lanes, huff, quant, scan_at, prog = build_blob(datas, infos)
     L = _library()
     st = stream if stream is not None else torch.cuda.current_stream(dev)
     with torch.cuda.device(dev), torch.cuda.stream(st):
         stage = torch.empty(int(hdr["total_bytes"]), dtype=torch.uint8, pin_memory=True)
         host = stage.numpy()
-        fill_blob(host, hdr, images, lanes, huff, quant, datas, infos, scan_at)
+        fill_blob(host, hdr, images, lanes, huff, quant, datas, infos, scan_at, prog)
         blob = stage.to(dev, non_blocking=True)                                  # the call's one host -> device copy
         coef = torch.empty(int(hdr["coef_elems"]), dtype=torch.int16, device=dev)
         planes = torch.empty(int(hdr["plane_bytes"]), dtype=torch.uint8, device=dev)
@@ -458,7 +713,7 @@ def decode(files, device=None, stream=None, ignore_orientation=False, check=True
             o, h, w = int(im["out_off"]), int(im["h"]), int(im["w"])
             frames.append(out[o:o + 3 * h * w].view(h, w, 3))
         if taps is not None:
-            taps.update(coef=coef, planes=planes, images=images, status=status, header=hdr)
+            taps.update(coef=coef, planes=planes, images=images, status=status, header=hdr, progressive=prog)
         if not check:
             return frames, status
         words = status.tolist()                                                  # the one synchronisation (it also keeps `stage` alive until the copy is done)

@@ -1,6 +1,6 @@
 """Measurements of the JPEG decoder (csrc/jpeg_decode.hip, maf-yolo_amd/jpeg.py) on the GPU; prints ONE JSON line.
 
-    python tools/jpeg_probe.py [--iters N] [--batches 32,256,1024]
+    python tools/jpeg_probe.py [--iters N] [--batches 32,256,1024] [--progressive]
 
 The file is the 480 x 640, 4:2:0, quality 90 case of tests/golden/jpeg_cases.npz replicated to B files per call.  Per B:
 * images/s of decode(files, check=False) end to end (host parse + staging + copy + the three kernels), wall clock over `iters` calls with
@@ -9,6 +9,10 @@ The file is the 480 x 640, 4:2:0, quality 90 case of tests/golden/jpeg_cases.npz
 * per-stage device times from event pairs around maf_jpeg_decode restricted to one stage (entropy includes the coefficient memset);
 * bytes moved per call: file bytes copied host -> device, coefficients written + read, planes written + read, frame bytes written.
 Where Pillow is importable, the single-thread Pillow decode time of the same file stands beside them.
+--progressive: the same picture as a progressive file (the 480 x 640 case of tests/golden/jpeg_progressive_cases.npz: 10 scans), decoded with
+progressive=True; per B additionally the launch count of a call (memsets aside: one entropy launch per scan round + IDCT + colour), the entropy
+stage as a whole (the coefficient memset and all rounds, which follow each other on the stream) and its mean per round, and under "baseline"
+the figures of the baseline file at the same B, measured in the same run.
 """
 import argparse
 import io
@@ -28,13 +32,13 @@ from maf_yolo_amd import jpeg as J, lib  # noqa: E402
 DEV = torch.device("cuda:0")
 
 
-def stage_times(files, iters):
+def stage_times(files, iters, progressive=False):
     """Event time of each stage alone, on buffers a full decode has filled."""
-    infos = [J.parse(f) for f in files]
-    hdr, images, lanes, huff, quant, scan_at = J.build_blob(files, infos)
+    infos = [J.parse(f, progressive) for f in files]
+    hdr, images, lanes, huff, quant, scan_at, prog = J.build_blob(files, infos)
     stage = torch.empty(int(hdr["total_bytes"]), dtype=torch.uint8, pin_memory=True)
     host = stage.numpy()
-    J.fill_blob(host, hdr, images, lanes, huff, quant, files, infos, scan_at)
+    J.fill_blob(host, hdr, images, lanes, huff, quant, files, infos, scan_at, prog)
     blob = stage.to(DEV)
     coef = torch.empty(int(hdr["coef_elems"]), dtype=torch.int16, device=DEV)
     planes = torch.empty(int(hdr["plane_bytes"]), dtype=torch.uint8, device=DEV)
@@ -58,46 +62,71 @@ def stage_times(files, iters):
         res[name + "_us"] = round(statistics.median(ts), 1)
     res["bytes"] = dict(h2d=int(hdr["total_bytes"]), coef_write_read=4 * int(hdr["coef_elems"]), planes_write_read=2 * int(hdr["plane_bytes"]),
                         frames=int(hdr["out_bytes"]), lanes=int((lanes["image"] >= 0).sum()))
+    if prog is not None:
+        rounds = int(hdr["n_rounds"])
+        res["launches"] = (1 if len(lanes) else 0) + rounds + 2
+        res["entropy_rounds"] = rounds
+        res["entropy_us_per_round_mean"] = round(res["entropy_us"] / rounds, 1)
+        res["bytes"]["scan_lanes"] = int((prog[1]["image"] >= 0).sum())
+        res["bytes"]["lanes_per_workgroup"] = int(hdr["sgroup"])
     return res
+
+
+def pillow_ms(data):
+    try:
+        from PIL import Image
+    except ImportError:
+        return None
+    ts = []
+    for _ in range(20):
+        t0 = time.perf_counter()
+        np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
+        ts.append(time.perf_counter() - t0)
+    return round(statistics.median(ts) * 1e3, 3)
+
+
+def measure(data, B, iters, progressive):
+    files = [data] * B
+    J.decode(files, device=DEV, progressive=progressive)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        J.decode(files, device=DEV, check=False, progressive=progressive)
+    t_enq = time.perf_counter() - t0
+    torch.cuda.synchronize()
+    t_async = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        J.decode(files, device=DEV, progressive=progressive)
+    t_sync = time.perf_counter() - t0
+    c = dict(B=B, img_s_check_false=round(B * iters / t_async, 1), img_s_check_true=round(B * iters / t_sync, 1),
+             host_enqueue_ms_per_call=round(t_enq / iters * 1e3, 2))
+    c.update(stage_times(files, max(3, iters), progressive))
+    torch.cuda.empty_cache()
+    return c
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--batches", default="32,256,1024")
+    ap.add_argument("--progressive", action="store_true", help="measure the progressive encoding of the same picture (and the baseline one beside it)")
     args = ap.parse_args()
-    z = np.load(os.path.join(ROOT, "tests", "golden", "jpeg_cases.npz"))
-    data = z["large_file"].tobytes()
+    data = np.load(os.path.join(ROOT, "tests", "golden", "jpeg_cases.npz"))["large_file"].tobytes()
     res = {"metric": "jpeg_probe", "file": "480x640 4:2:0 q90, %d bytes" % len(data), "cases": {}}
-    try:
-        from PIL import Image
-        ts = []
-        for _ in range(20):
-            t0 = time.perf_counter()
-            np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
-            ts.append(time.perf_counter() - t0)
-        res["pillow_single_thread_ms"] = round(statistics.median(ts) * 1e3, 3)
-    except ImportError:
-        res["pillow_single_thread_ms"] = None
+    res["pillow_single_thread_ms"] = pillow_ms(data)
+    if args.progressive:
+        pdata = np.load(os.path.join(ROOT, "tests", "golden", "jpeg_progressive_cases.npz"))["large_file"].tobytes()
+        res["metric"] = "jpeg_probe_progressive"
+        res["progressive_file"] = "480x640 4:2:0 q90 progressive (10 scans), %d bytes" % len(pdata)
+        res["pillow_single_thread_ms_progressive"] = pillow_ms(pdata)
     for B in [int(b) for b in args.batches.split(",")]:
-        files = [data] * B
-        J.decode(files, device=DEV)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(args.iters):
-            J.decode(files, device=DEV, check=False)
-        t_enq = time.perf_counter() - t0
-        torch.cuda.synchronize()
-        t_async = time.perf_counter() - t0
-        t0 = time.perf_counter()
-        for _ in range(args.iters):
-            J.decode(files, device=DEV)
-        t_sync = time.perf_counter() - t0
-        c = dict(B=B, img_s_check_false=round(B * args.iters / t_async, 1), img_s_check_true=round(B * args.iters / t_sync, 1),
-                 host_enqueue_ms_per_call=round(t_enq / args.iters * 1e3, 2))
-        c.update(stage_times(files, max(3, args.iters)))
+        if args.progressive:
+            c = measure(pdata, B, args.iters, True)
+            c["baseline"] = measure(data, B, args.iters, False)
+        else:
+            c = measure(data, B, args.iters, False)
         res["cases"][str(B)] = c
-        torch.cuda.empty_cache()
     print(json.dumps(res))
 
 
