@@ -697,6 +697,43 @@ int maf_mosaic_affine(const maf_augment_sample_t* samples, const maf_augment_sam
                       maf_stream_t stream);
 
 /*
+ * maf_resize_area: load_image's cv2.resize INTER_AREA of an evaluation frame larger than the load size (yolov6/data/datasets.py:277-300 with
+ * r < 1 and augment off), n frames in one launch, uint8 HWC in, uint8 HWC out.  Both axes shrink or stay (new_w <= w, new_h <= h); the pixel
+ * rule is OpenCV's as restated in tests/area_ref.py, bit for bit.  The caller (maf-yolo_amd/letterbox.py) picks the path of every frame with
+ * OpenCV's own test and builds the decimation tables in double; the device only multiplies, adds and rounds.
+ *   frames [n]    HOST table (validated); frames_dev: DEVICE copy of the same table, read by the kernel (always required)
+ *   src           DEVICE, uint8 HWC (3 channels, pixel stride 3, row pitch src_pitch >= 3 w bytes, any alignment); reads stay in
+ *                 [row * pitch, + 3 w) of rows < h
+ *   dst           DEVICE, uint8 HWC new_h x new_w, pitch 3 new_w, no alignment needed; every byte written once; must not overlap any src
+ *   path          MAF_AREA_FAST2: the 2 x 2 average (a + b + c + d + 2) >> 2, iscale_x = iscale_y = 2;  MAF_AREA_FASTN: the integer sum of
+ *                 the iscale_y x iscale_x block times inv_area = 1.0f / (iscale_x iscale_y) in fp32, rounded half to even (1 x 1: a copy);
+ *                 both need w = iscale_x new_w and h = iscale_y new_h.  MAF_AREA_GENERAL: the tables below.
+ *   tables        HOST copy of the table words (int32), tables_dev its DEVICE copy, table_words their count; may be NULL / 0 when no frame
+ *                 takes the general path.  Per axis of a general-path frame, at word offsets from the start of the tables: x_start / y_start
+ *                 -> start [n_dst + 1] (entry range of every destination index, rising from 0), x_pairs / y_pairs (even) -> the entries,
+ *                 two words each: source index, fp32 alpha.  Frames of one size share their tables.
+ * Validates everything above on the host copies — every table offset and every source index of every table included — before touching the
+ * device.  maf_area_struct_sizes: sizeof(maf_area_frame_t), for bindings to check their mirror.
+ */
+#define MAF_AREA_FAST2 0
+#define MAF_AREA_FASTN 1
+#define MAF_AREA_GENERAL 2
+typedef struct {
+    const uint8_t* src; int64_t src_pitch;
+    int32_t h, w;                        /* source frame */
+    uint8_t* dst;
+    int32_t new_h, new_w;                /* shrunk frame, pitch 3 new_w */
+    int32_t path;                        /* MAF_AREA_* */
+    int32_t iscale_x, iscale_y;          /* the fast paths' integer factors */
+    float inv_area;                      /* 1.0f / (iscale_x iscale_y) */
+    int32_t x_start, x_pairs;            /* the general path's tables, word offsets */
+    int32_t y_start, y_pairs;
+} maf_area_frame_t;
+int maf_area_struct_sizes(int32_t* frame_size);
+int maf_resize_area(const maf_area_frame_t* frames, const maf_area_frame_t* frames_dev, int32_t n, const void* tables, const void* tables_dev,
+                    int64_t table_words, maf_stream_t stream);
+
+/*
  * In-process precision / recall / mAP of an evaluation (the do_pr_metric path of Evaler.predict_model, yolov6/core/evaler.py:195-268, with
  * yolov6/utils/metrics.py process_batch, ConfusionMatrix, ap_per_class, compute_ap); the rules are those of tests/pr_metric_ref.py.
  * Every pointer below is a DEVICE pointer; nothing synchronises the host.

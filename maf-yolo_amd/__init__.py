@@ -6,7 +6,7 @@ from .lib import MafError  # noqa: F401
 from .model import Model, Detect_yaml  # noqa: F401
 from .nms import non_max_suppression, non_max_suppression_async, nms_raw  # noqa: F401
 from .post import convert_to_coco_format, coco_rows  # noqa: F401
-from .letterbox import letterbox, eval_batch, rescale_boxes, detect_frames  # noqa: F401
+from .letterbox import letterbox, eval_batch, rescale_boxes, detect_frames, resize_area  # noqa: F401
 from .augment import TrainAugment, train_batch  # noqa: F401
 from . import metrics  # noqa: F401
 from .metrics import PrMetric  # noqa: F401

@@ -6,12 +6,15 @@ The layer in front of Model.forward and behind non_max_suppression that the refe
                              engine takes (the / 255 stays folded into the stem);
   * eval_batch(frames, ...)  TrainValDataset.load_image + the rect letterbox of __getitem__ (yolov6/data/datasets.py:277-300, :196-213) with
                              the batch shape of sort_files_shapes (:670-695): (imgs, shapes) as collate_fn hands them to the Evaler;
+  * resize_area(frames, sizes)  load_image's cv2.resize INTER_AREA of evaluation frames larger than the load size (datasets.py:294-300, r < 1):
+                             ONE kernel (csrc/resize_area.hip) for a list of frames; eval_batch(area=True) runs it in front of the letterbox
+                             launch for the frames that need it (opt-in: without the flag such frames raise MafError as before);
   * rescale_boxes(dets, ...) Inferer.rescale (inferer.py:181-195) + .round() (:98), in place on the device;
   * detect_frames(model, frames, ...)  the Inferer.infer loop (inferer.py:71-98) for a batch: letterbox -> model -> NMS -> rescale, one
                              device -> host copy (the per-image counts).
 The geometry (scale, unpadded size, padding) is host bookkeeping with the reference's own formulas, Python's round-half-even round() included
 (tests/golden/letterbox_cases.npz holds what the reference's code computes).  The pixels follow OpenCV's uint8 INTER_LINEAR as restated in
-tests/letterbox_ref.py, bit for bit.  No CPU fallback: CPU or non-uint8 frames raise MafError.
+tests/letterbox_ref.py and its uint8 INTER_AREA as restated in tests/area_ref.py, bit for bit.  No CPU fallback: CPU or non-uint8 frames raise MafError.
 """
 import math
 
@@ -56,13 +59,21 @@ def letterbox_geometry(h, w, new_shape=(640, 640), auto=True, scaleup=True, stri
                 ret=(r, (left, top)) if return_int else (r, (dw, dh)))
 
 
-def load_image_size(h0, w0, img_size=640):
-    """TrainValDataset.load_image (datasets.py:277-300) in evaluation (augment = False), without the pixels -> (r, (h, w)).  r < 1 means
-    OpenCV INTER_AREA with a non-integer factor in the reference: out of scope here (MafError)."""
-    r = img_size / max(h0, w0)
+def load_image_size(h0, w0, img_size=640, load_size=None, area=False):
+    """TrainValDataset.load_image (datasets.py:277-300) in evaluation (augment = False), without the pixels -> (r, (h, w)).  `load_size` is
+    the reference's force_load_size (hyp["test_load_size"]; None: img_size).  r < 1 means OpenCV INTER_AREA in the reference: MafError unless
+    area=True (resize_area does it then)."""
+    r = (load_size if load_size else img_size) / max(h0, w0)
     if r < 1:
-        raise MafError("eval_batch: a %d x %d frame is larger than img_size = %d: the reference shrinks it with OpenCV INTER_AREA, which this "
-                       "package does not implement (frames up to img_size on the longest side: COCO val is covered)" % (h0, w0, img_size))
+        if not area:
+            raise MafError("eval_batch: a %d x %d frame is larger than img_size = %d: the reference shrinks it with OpenCV INTER_AREA, which this "
+                           "package does not implement (frames up to img_size on the longest side: COCO val is covered)"
+                           % (h0, w0, load_size if load_size else img_size))
+        h, w = int(h0 * r), int(w0 * r)
+        if h < 1 or w < 1:
+            raise MafError("eval_batch: a %d x %d frame shrinks to %d x %d at load size %d: cv2.resize fails on an empty size"
+                           % (h0, w0, h, w, load_size if load_size else img_size))
+        return r, (h, w)
     if r != 1:
         return r, (int(h0 * r), int(w0 * r))
     return r, (h0, w0)
@@ -81,23 +92,79 @@ def rect_batch_shape(hw0, img_size=640, stride=32, pad=0.5):
     return (np.ceil(np.array(shape) * img_size / stride + pad).astype(np.int64) * stride).tolist()
 
 
-def eval_geometry(h0, w0, batch_shape, img_size=640):
-    """load_image + letterbox(img, batch_shape, auto=False, scaleup=False) of __getitem__ -> dict(new_unpad, top, left, shape, shapes):
-    `shapes` = ((h0, w0), ((h * ratio / h0, w * ratio / w0), pad)), what convert_to_coco_format consumes."""
-    _, (h, w) = load_image_size(h0, w0, img_size)
-    g = letterbox_geometry(h, w, tuple(batch_shape), auto=False, scaleup=False)
-    if g["new_unpad"] != (w, h):
+def eval_geometry(h0, w0, batch_shape, img_size=640, load_size=None, return_int=False, area=False):
+    """load_image + letterbox(img, batch_shape, auto=False, scaleup=False) of __getitem__ -> dict(new_unpad, top, left, shape, shapes, load):
+    `shapes` = ((h0, w0), ((h * ratio / h0, w * ratio / w0), pad)), what convert_to_coco_format consumes; `return_int` makes pad the
+    (left, top) of hyp["letterbox_return_int"]; `load` names load_image's resize: "area" (r < 1, needs area=True), "linear" (r > 1) or None.
+    A frame that took the area path may be shrunk again by the letterbox (two resizes, as the reference does); any other frame may not."""
+    r, (h, w) = load_image_size(h0, w0, img_size, load_size, area)
+    load = "area" if r < 1 else ("linear" if r != 1 else None)
+    g = letterbox_geometry(h, w, tuple(batch_shape), auto=False, scaleup=False, return_int=return_int)
+    if g["new_unpad"] != (w, h) and load != "area":
         raise MafError("eval_batch: batch shape %s is smaller than the %d x %d loaded frame: the reference would resize twice (load_image, then "
                        "letterbox); not supported" % (list(batch_shape), h, w))
     ratio, pad = g["ret"]
     g["shapes"] = ((h0, w0), ((h * ratio / h0, w * ratio / w0), pad))
     g["load_hw"] = (h, w)
+    g["load"] = load
     return g
+
+
+# ---------------------------------------------------------------- INTER_AREA tables (host)
+
+DBL_EPSILON = float(np.finfo(np.float64).eps)
+# maf_area_frame_t (include/mafyolo_hip.h)
+AREA_FRAME_DT = np.dtype([("src", "<u8"), ("src_pitch", "<i8"), ("h", "<i4"), ("w", "<i4"), ("dst", "<u8"), ("new_h", "<i4"), ("new_w", "<i4"),
+                          ("path", "<i4"), ("iscale_x", "<i4"), ("iscale_y", "<i4"), ("inv_area", "<f4"),
+                          ("x_start", "<i4"), ("x_pairs", "<i4"), ("y_start", "<i4"), ("y_pairs", "<i4")], align=True)
+
+
+def area_plan(h, w, new_h, new_w):
+    """The path cv2.resize(..., INTER_AREA) takes for h x w -> new_h x new_w (both axes shrink or stay), by OpenCV's own test in double:
+    scale = 1.0 / (new / old), iscale = round-half-even(scale), fast when |scale - iscale| < DBL_EPSILON on both axes
+    -> (lib.AREA_FAST2 | AREA_FASTN | AREA_GENERAL, iscale_x, iscale_y)."""
+    scale_x, scale_y = 1.0 / (new_w / w), 1.0 / (new_h / h)
+    ix, iy = int(round(scale_x)), int(round(scale_y))
+    if abs(scale_x - ix) < DBL_EPSILON and abs(scale_y - iy) < DBL_EPSILON:
+        if ix * new_w != w or iy * new_h != h:
+            raise MafError("resize_area: %d x %d -> %d x %d passes OpenCV's integer-factor test without exact factors" % (h, w, new_h, new_w))
+        return (lib.AREA_FAST2 if ix == 2 and iy == 2 else lib.AREA_FASTN), ix, iy
+    return lib.AREA_GENERAL, ix, iy
+
+
+def area_table(n_src, n_dst):
+    """OpenCV's computeResizeAreaTab for one axis, in double -> (start int32 [n_dst + 1], src index int32 [k], alpha float32 [k]): destination
+    index d owns entries start[d] .. start[d + 1] - 1, in OpenCV's order (the partial source cell in front, the whole cells, the partial
+    cell behind; a partial cell counts when it is wider than 1e-3)."""
+    scale = 1.0 / (n_dst / n_src)
+    d = np.arange(n_dst, dtype=np.float64)
+    f1 = d * scale
+    f2 = f1 + scale
+    cell = np.minimum(scale, n_src - f1)
+    s2 = np.minimum(np.floor(f2).astype(np.int64), n_src - 1)
+    s1 = np.minimum(np.ceil(f1).astype(np.int64), s2)
+    head, tail, mid = (s1 - f1) > 1e-3, (f2 - s2) > 1e-3, s2 - s1
+    count = head + mid + tail
+    if (count < 1).any() or (mid < 0).any():
+        raise MafError("resize_area: %d -> %d leaves a destination index without a source cell" % (n_src, n_dst))
+    start = np.concatenate([[0], np.cumsum(count)])
+    si, alpha = np.empty(start[-1], np.int64), np.empty(start[-1], np.float64)
+    pos = start[:-1]
+    si[pos[head]], alpha[pos[head]] = s1[head] - 1, ((s1 - f1) / cell)[head]
+    rep = np.repeat(np.arange(n_dst), mid)
+    j = np.arange(rep.size) - np.repeat(np.cumsum(mid) - mid, mid)
+    at = pos[rep] + head[rep] + j
+    si[at], alpha[at] = s1[rep] + j, (1.0 / cell)[rep]
+    at = (pos + head + mid)[tail]
+    si[at], alpha[at] = s2[tail], (np.minimum(np.minimum(f2 - s2, 1.0), cell) / cell)[tail]
+    if si.min() < 0 or si.max() >= n_src:
+        raise MafError("resize_area: %d -> %d names a source index outside the frame" % (n_src, n_dst))
+    return start.astype(np.int32), si.astype(np.int32), alpha.astype(np.float32)
 
 
 # ---------------------------------------------------------------- device
 
-def _frame_list(frames):
+def _frame_list(frames, what="letterbox"):
     if torch.is_tensor(frames):
         if frames.dim() != 4:
             raise MafError("letterbox: a single tensor of frames is uint8 [B, h, w, 3]")
@@ -107,7 +174,7 @@ def _frame_list(frames):
         raise MafError("letterbox: no frames")
     for f in frames:
         if not torch.is_tensor(f) or not f.is_cuda:
-            raise MafError("letterbox runs on the HIP path only: frames must be CUDA tensors (no CPU fallback)")
+            raise MafError("%s runs on the HIP path only: frames must be CUDA tensors (no CPU fallback)" % what)
         if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3:
             raise MafError("letterbox: frames are uint8 [h, w, 3] tensors, got %s %s" % (f.dtype, tuple(f.shape)))
         if f.stride(2) != 1 or f.stride(1) != 3:
@@ -151,15 +218,117 @@ def letterbox(frames, new_shape=640, color=(114, 114, 114), auto=True, scaleup=T
     return imgs, [g["ret"][0] for g in geoms], [g["ret"][1] for g in geoms]
 
 
-def eval_batch(frames, img_size=640, stride=32, pad=0.5, shape=None, bgr=True):
+_area_checked = False
+
+
+def _area_tables(frames, sizes):
+    """The host half of resize_area -> (frame table [n] of AREA_FRAME_DT with dst as an offset into the output, the table words int32 [k],
+    output bytes): paths by area_plan, one decimation-table set per distinct (source, destination) size pair of an axis."""
+    tab = np.zeros(len(frames), AREA_FRAME_DT)
+    words, at, n_words, off = [], {}, 0, 0
+
+    def axis(n_src, n_dst):
+        nonlocal n_words
+        if (n_src, n_dst) not in at:
+            start, si, alpha = area_table(n_src, n_dst)
+            pairs = np.empty(2 * si.size, np.int32)
+            pairs[0::2], pairs[1::2] = si, alpha.view(np.int32)
+            pad = np.zeros((start.size + n_words) & 1, np.int32)           # the pairs start on an even word (64-bit loads)
+            at[(n_src, n_dst)] = (n_words, n_words + start.size + pad.size)
+            words.extend([start, pad, pairs])
+            n_words += start.size + pad.size + pairs.size
+        return at[(n_src, n_dst)]
+
+    for i, (f, (nh, nw)) in enumerate(zip(frames, sizes)):
+        h, w = int(f.shape[0]), int(f.shape[1])
+        if nh < 1 or nw < 1 or h < 1 or w < 1:
+            raise MafError("resize_area: frame %d: %d x %d -> %d x %d: sizes must be positive" % (i, h, w, nh, nw))
+        if nh > h or nw > w:
+            raise MafError("resize_area: frame %d: %d x %d -> %d x %d grows an axis (INTER_AREA shrinks; OpenCV turns a growing axis into a "
+                           "linear variant, which load_image cannot reach)" % (i, h, w, nh, nw))
+        path, ix, iy = area_plan(h, w, nh, nw)
+        e = tab[i]
+        e["src"], e["src_pitch"], e["h"], e["w"], e["new_h"], e["new_w"] = f.data_ptr(), f.stride(0), h, w, nh, nw
+        e["path"], e["iscale_x"], e["iscale_y"] = path, ix, iy
+        e["inv_area"] = np.float32(1.0) / np.float32(ix * iy)
+        if path == lib.AREA_GENERAL:
+            (e["x_start"], e["x_pairs"]), (e["y_start"], e["y_pairs"]) = axis(w, nw), axis(h, nh)
+        e["dst"] = off                                                     # + the allocation's address, once it exists
+        off += 3 * nh * nw
+    return tab, (np.concatenate(words) if words else np.zeros(0, np.int32)), off
+
+
+def _area_library():
+    """The HIP library, with the frame struct of this binding checked against it once."""
+    global _area_checked
+    L = lib.load()
+    if not _area_checked:
+        import ctypes
+        size = (ctypes.c_int32 * 1)()
+        lib.check(L.maf_area_struct_sizes(size))
+        if size[0] != AREA_FRAME_DT.itemsize:
+            raise MafError("libmafyolo_hip.so was built for a maf_area_frame_t of %d bytes, this binding declares %d: rebuild" % (size[0], AREA_FRAME_DT.itemsize))
+        _area_checked = True
+    return L
+
+
+def resize_area(frames, sizes, stream=None):
+    """cv2.resize(frame, (new_w, new_h), interpolation=cv2.INTER_AREA) for a list of frames whose axes shrink or stay, in one launch.
+    frames: uint8 [h_i, w_i, 3] CUDA tensors (views and crops welcome); sizes: one (new_h, new_w) per frame.  -> a list of uint8
+    [new_h_i, new_w_i, 3] tensors, views of one allocation.  The frame table and the decimation tables (one set per distinct size pair)
+    travel in one pinned blob with one host -> device copy; nothing synchronises the host.  `stream`: a torch.cuda.Stream to work on
+    (default: the current one)."""
+    frames = _frame_list(frames, "resize_area")
+    sizes = [(int(s[0]), int(s[1])) for s in sizes]
+    if len(sizes) != len(frames):
+        raise MafError("resize_area: %d sizes for %d frames" % (len(sizes), len(frames)))
+    dev = frames[0].device
+    if any(f.device != dev for f in frames):
+        raise MafError("resize_area: the frames of a call live on one device")
+    tab, words, total = _area_tables(frames, sizes)
+    L = _area_library()
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev), torch.cuda.stream(st):
+        out = torch.empty(total, dtype=torch.uint8, device=dev)
+        tab["dst"] += np.uint64(out.data_ptr())
+        tab_bytes = tab.nbytes                                            # a multiple of 8: the table words behind it stay aligned
+        stage = torch.empty(tab_bytes + words.nbytes, dtype=torch.uint8, pin_memory=True)
+        host = stage.numpy()
+        host[:tab_bytes] = tab.view(np.uint8)
+        host[tab_bytes:] = words.view(np.uint8)
+        blob = stage.to(dev, non_blocking=True)                           # the call's one host -> device copy
+        lib.check(L.maf_resize_area(host.ctypes.data, blob.data_ptr(), len(frames), host.ctypes.data + tab_bytes if words.size else None,
+                                    blob.data_ptr() + tab_bytes if words.size else None, words.size, st.cuda_stream))
+    res, off = [], 0
+    for nh, nw in sizes:
+        res.append(out[off:off + 3 * nh * nw].view(nh, nw, 3))
+        off += 3 * nh * nw
+    return res
+
+
+def eval_batch(frames, img_size=640, stride=32, pad=0.5, shape=None, bgr=True, area=False, load_size=None, return_int=False, rect=True):
     """The evaluation loader's batch (load_image + rect letterbox + collate_fn) from decoded frames -> (imgs uint8 [B, 3, H, W], shapes): the
-    batch shape is `shape` ([H, W]) or the sort_files_shapes rule over this batch's aspect ratios; `shapes` is the per-image tuple that
-    EvalLoop / convert_to_coco_format consume."""
-    frames = _frame_list(frames)
+    batch shape is `shape` ([H, W]), [img_size, img_size] with rect=False (the reference's not_infer_on_rect), or the sort_files_shapes rule
+    over this batch's aspect ratios with `pad` (0.0: force_no_pad); `shapes` is the per-image tuple that EvalLoop / convert_to_coco_format
+    consume.  `load_size` is hyp["test_load_size"], `return_int` hyp["letterbox_return_int"].  With area=True the frames whose longest side
+    exceeds the load size are shrunk by one resize_area launch (OpenCV INTER_AREA) in front of the letterbox launch, which then copies them,
+    or shrinks them again linearly where the batch shape demands it; every other frame takes the single launch as before.  Without
+    area=True such frames raise MafError.  The reference's eval_640_repro recipe:
+    eval_batch(frames, 640, pad=0.0, rect=False, area=True, load_size=638, return_int=True), then EvalLoop(..., scale_exact=True)."""
+    frames = _frame_list(frames, "eval_batch" if area else "letterbox")
     hw0 = [(int(f.shape[0]), int(f.shape[1])) for f in frames]
-    bs = list(shape) if shape is not None else rect_batch_shape(hw0, img_size, stride, pad)
-    geoms = [eval_geometry(h0, w0, bs, img_size) for h0, w0 in hw0]
+    if shape is not None:
+        bs = list(shape)
+    elif not rect:
+        bs = [int(img_size), int(img_size)]
+    else:
+        bs = rect_batch_shape(hw0, img_size, stride, pad)
+    geoms = [eval_geometry(h0, w0, bs, img_size, load_size, return_int, area) for h0, w0 in hw0]
     H, W = geoms[0]["shape"]
+    shrink = [i for i, g in enumerate(geoms) if g["load"] == "area"]
+    if shrink:
+        for i, small in zip(shrink, resize_area([frames[i] for i in shrink], [geoms[i]["load_hw"] for i in shrink])):
+            frames[i] = small
     imgs = _launch(frames, H, W, geoms, (114, 114, 114), bgr)
     return imgs, tuple(g["shapes"] for g in geoms)
 
