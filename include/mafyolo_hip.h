@@ -345,6 +345,8 @@ int maf_loss_terms(const void* pred_scores, const void* pred_distri, int32_t dty
 /* BatchNorm2d in training mode fused with the activation behind it (Conv.forward = act(bn(conv(x))), common.py:46-47), NHWC views.
  *   maf_bn_forward   batch statistics -> save_mean / save_rstd (+ running stats with torch's momentum rule, unbiased variance, and
  *                    the int64 num_batches_tracked counter += 1; each may be NULL) and y = act(xhat*gamma + beta); two launches (statistics, apply).
+ *                    The statistics launch accumulates {sum x, sum (x - p)^2} about a per-channel pivot p that both launches read from x (csrc/bn_act.hip);
+ *                    the apply pass re-reads those pixels in every workgroup, so y MUST NOT alias x (refused).
  *   maf_bn_backward  dz = gradient w.r.t. the activation output; recomputes u from x; dx, dgamma, dbeta; two launches.
  *   residual         (may be NULL) a tensor like y added BEFORE the activation: y = act(xhat*gamma + beta + residual) — the branch sums of
  *                    RepVGGBlock (common.py:224) and DilatedReparamBlock (:3028-3031) without their own pass.  Backward needs it only when the
@@ -381,7 +383,9 @@ int maf_bn_forward_ex(const void* x, int32_t x_stride, int32_t M, int32_t C, int
                       int32_t y_stride, float* save_mean, float* save_rstd, float* part, int32_t R, int32_t phase, const void* residual, int32_t res_stride,
                       int32_t stats_ready, maf_stream_t stream);
 int32_t maf_bn_replicas(int32_t C, int32_t R);
-/* The statistics pass of maf_bn_forward alone (half `phase` of `part` += {sum x, sum x^2}; nothing is cleared). */
+/* The statistics pass alone, about NO pivot (half `phase` of `part` += {sum x, sum x^2}, what maf_bn_forward_ex(stats_ready = 1) and maf_bn_sum_forward
+ * expect — unlike maf_bn_forward's own launch, whose second sum is sum (x - p)^2; nothing is cleared).  Raw sums lose digits as |mean| / std grows (fp32 rows of
+ * 3200 x 576 at |mean| / std = 32: save_rstd 2.4e-4 off fp64). */
 int maf_bn_stats(const void* x, int32_t x_stride, int32_t M, int32_t C, int32_t dtype, float* part, int32_t R, int32_t phase, maf_stream_t stream);
 /* The SUM of the nb (2..4) training-mode BatchNorm2d of a DilatedReparamBlock (common.py:3024-3031: origin_bn(lk_origin(x)) + sum_j dil_bn_j(dil_conv_j(x)),
  * no activation; act = MAF_ACT_RELU: RepVGGBlock's ReLU(BN(3x3 s2) + BN(1x1 s2)), common.py:224 — the backward recomputes the sum for the ReLU's mask)

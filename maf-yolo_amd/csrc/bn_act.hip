@@ -12,6 +12,26 @@
 // [2][R][2][roundup(C,256)]: a call accumulates into half `phase` and its apply kernel clears half `1 - phase` — the one the
 // previous call on the stream used and everybody has finished with — so one buffer per stream, zeroed once, serves every BatchNorm
 // of a step without memsets or finalize launches; the caller alternates `phase`.
+//
+// Accuracy.  The variance is one-pass, E x^2 - (E x)^2 with the sums in fp32 (lanes, shuffles, LDS and global atomics) and the fold in double, which loses
+// digits as |mean| / std grows.  maf_bn_forward's own statistics launch therefore takes the SECOND sum about a pivot, q = sum (x - p)^2 with p[c] = the median of
+// three pixels of the tensor itself (pivot_pixel below: pixel 0 and two golden-section positions) — every workgroup of both kernels reads them from x (no buffer,
+// no protocol; y must therefore not alias x, which maf_bn_forward_ex refuses), three loads per thread up front and one subtract per element (tools/bn_bench.py,
+// 32 x 160 x 160 x 48 and 32 x 20 x 20 x 768 fp16: DESIGN.md's BatchNorm accuracy paragraph holds the timings beside the parent's) — and the apply pass takes
+// var = q/M - (mean - p)^2.  A sample of the channel is a few std from its mean whatever that mean is; the median of three stays one when ONE of them is not
+// (the corner of a zero-padded conv, an activation outlier: tested with pixel 0 at 0, 4/9 and 5 x the mean, 18 to 128 std out).  A constant channel and M = 1 give var = 0 exactly (with
+// sum x^2, fl(x^2) - x^2 survived: rstd 4e-4 off at M = 1).  The FIRST sum stays sum x: the mean is the number it
+// always was (about a pivot its fp32 round-off would scale with |mean - p| instead of |mean| — worse for the usual |mean| < std).  Measured with sum x^2:
+// save_rstd of fp32 3200 x 576 rows at |mean| / std = 32 was 2.4e-4 off against a bar of 1e-4.  The apply pass evaluates u = (x - mean)*sc + beta, the form the
+// backward pass recomputes u in (x*sc + (beta - mean*sc) cancels two terms of size |mean| * rstd: 3 % of y's range for a one-pixel channel at |x| ~ 1e4).
+// NOT covered: maf_bn_stats and the producers' epilogues (1x1 conv, depth-wise branches, csrc/bn_sum.hip's STATS form; stats_ready = 1) hand over
+// {sum x, sum x^2}, pivot 0, for fp16 AND fp32 tensors.  fp16 tensors meet the fp16 bars below up to |mean| / std = 32.  fp32 tensors (the fp32 training leg
+// feeds these paths too) are tested through maf_bn_stats on 4800 x 72 rows only, where raw sums pass; on wider or longer fp32 rows at |mean| / std = 32 raw sums
+// miss the fp32 statistics bar (the 2.4e-4 above) — a known limit of these four paths, not of maf_bn_forward.
+// Tested to (tests/test_gpu_bn_stats.py, every figure against fp64 on the stored values, max |err| / max |ref|; save_rstd and running_var relative per channel):
+// (mean, std) in {(0.4, 1.7), (4, 0.5), (+-8, 0.25), (8, 1)} x {4800 x 72, 102400 x 24, 25600 x 96, 3200 x 576} pixels x channels x {fp32, fp16} x {SiLU, none}:
+// fp32 2e-4 for y, 4e-4 for dx / dgamma / dbeta, 1e-4 for save_mean / save_rstd / the running statistics; fp16 storage 1e-2, 2e-2, 2e-3.  (16, 0.25), ratio 64:
+// held to ten times those bars as a gross-error check; what it measures is in DESIGN.md §4.
 #include <cstdlib>
 #include "maf_common.h"
 
@@ -30,6 +50,7 @@ struct BnArgs2 {
     const void* res; void* dres; int rs, drs;          // residual added before the activation (forward, and backward when the activation needs u); d residual out
     int acc_affine;                                   // backward: dgamma / dbeta are ADDED to what the buffers hold (a gradient-exchange bucket slice)
     float* det;                                       // deterministic mode (maf_set_deterministic): per-workgroup sums [gridDim.x][2][C], no atomics anywhere
+    int pivot;                                        // forward: the second sum is of (x - p[c])^2, p = pivot_pixel's median (the header comment); 0: of x^2 (maf_bn_stats, the producers' epilogues)
 };
 
 template <typename T> struct Vec;
@@ -49,6 +70,12 @@ __device__ __forceinline__ float act_grad(float u, int act) {       // d act / d
 
 constexpr int kMaxR = 16;                                            // replicas actually used: min(R, kMaxR, 1024 / C)
 constexpr int kU = 4;                                                // independent 16-byte loads in flight per lane and tensor
+
+// The pivot of the forward statistics (header comment): per channel the MEDIAN of the tensor's pixels 0, ~0.382 M and ~0.618 M — every workgroup of both kernels
+// computes the same number from the tensor itself.  One pixel alone may be anything (the corner of a zero-padded conv holds ~4/9 of the channel's mean, an
+// activation outlier is arbitrarily far out) and a pivot many std from the mean brings the cancellation back; the median shrugs off one such pixel, and the two
+// golden-section positions fall on no fixed row or column of a B x H x W map.
+__device__ __forceinline__ int pivot_pixel(int M, int k) { return k == 0 ? 0 : (int)(((long long)M * (k == 1 ? 25043 : 40493)) >> 16); }     // < M for M >= 1
 
 // BWD = false: part += {sum x, sum x^2};  BWD = true: part += {sum g, sum g*xhat}
 // workgroup = a SLICE of at most 8 channel groups (blockIdx.y; 128 B of a pixel row) x a chunk of pixels (blockIdx.x); thread = one
@@ -84,17 +111,24 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const BnArgs2 a) {
     const T* dp = static_cast<const T*>(a.dz);
     const int gl = threadIdx.x % gsl, pl = threadIdx.x / gsl, gi = gbeg + gl;
     const bool active = gl < gcnt && pl < plan;
-    float s0[N], s1[N], mu[N], rs[N], ga[N], be[N];
+    float s0[N], s1[N], mu[N], rs[N], ga[N], be[N], pv[N];
 #pragma unroll
     for (int j = 0; j < N; ++j) {
-        s0[j] = s1[j] = 0.f;
+        s0[j] = s1[j] = pv[j] = 0.f;
         if (BWD && active) { mu[j] = a.mean[gi * N + j]; rs[j] = a.rstd[gi * N + j]; ga[j] = a.gamma[gi * N + j]; be[j] = a.beta[gi * N + j]; }
+    }
+    if (!BWD && a.pivot && active) {                                 // the pivot (pivot_pixel): the same value in every workgroup
+        const V x0 = *reinterpret_cast<const V*>(xp + gi * N);
+        const V x1 = *reinterpret_cast<const V*>(xp + (size_t)pivot_pixel(a.M, 1) * a.xs + gi * N);
+        const V x2 = *reinterpret_cast<const V*>(xp + (size_t)pivot_pixel(a.M, 2) * a.xs + gi * N);
+#pragma unroll
+        for (int j = 0; j < N; ++j) pv[j] = __builtin_amdgcn_fmed3f((float)x0[j], (float)x1[j], (float)x2[j]);
     }
     const T* rp = static_cast<const T*>(a.res);
     auto accum = [&](const V& xv, const V& dv, const V& rv) {
         if (!BWD) {
 #pragma unroll
-            for (int j = 0; j < N; ++j) { const float f = (float)xv[j]; s0[j] += f; s1[j] = __builtin_fmaf(f, f, s1[j]); }
+            for (int j = 0; j < N; ++j) { const float f = (float)xv[j], d = f - pv[j]; s0[j] += f; s1[j] = __builtin_fmaf(d, d, s1[j]); }
         } else {
 #pragma unroll
             for (int j = 0; j < N; ++j) {
@@ -195,9 +229,14 @@ template <typename T, bool BWD, bool RES = false, int ACT = MAF_ACT_NONE>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const BnArgs2 a) {
     typedef typename Vec<T>::type V;
     constexpr int N = Vec<T>::N;
-    extern __shared__ float cst[];                                    // forward [2][C]: sc, sh;  backward [6][C]: mu, rs, ga, be, k0, k1
+    extern __shared__ float cst[];                                    // forward [3][C]: sc, mu, be;  backward [6][C]: mu, rs, ga, be, k0, k1
     const float invM = 1.f / (float)a.M;
     for (int c = threadIdx.x; c < a.C; c += 256) {
+        float px = 0.f;                                               // the pivot of channel c — what bn_stats_kernel subtracted; its loads issued with the replica loads, not behind their adds
+        if (!BWD && a.pivot) {
+            const T* x0 = static_cast<const T*>(a.x) + c;
+            px = __builtin_amdgcn_fmed3f((float)x0[0], (float)x0[(size_t)pivot_pixel(a.M, 1) * a.xs], (float)x0[(size_t)pivot_pixel(a.M, 2) * a.xs]);
+        }
         float v0[kMaxR], v1[kMaxR];                                   // all replica loads in flight before the first add
 #pragma unroll
         for (int r = 0; r < kMaxR; ++r) {
@@ -208,12 +247,15 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const BnArgs2 a) {
 #pragma unroll
         for (int r = 0; r < kMaxR; ++r) { s += v0[r]; q += v1[r]; }
         if (!BWD) {
-            const double mu = s / a.M;
-            double var = q / a.M - mu * mu;                          // biased (normalisation)
+            const double p = a.pivot ? (double)px : 0.0;
+            const double mu = s / a.M, dm = mu - p;                 // q = sum (x - p)^2:  var = E (x - p)^2 - (mu - p)^2
+            double var = q / a.M - dm * dm;                          // biased (normalisation)
             if (var < 0) var = 0;
             const float muf = (float)mu, rsf = (float)(1.0 / sqrt(var + (double)a.eps));
             const float sc = rsf * a.gamma[c];
-            cst[c] = sc; cst[a.C + c] = a.beta[c] - muf * sc;         // u = x*sc + sh
+            // u = (x - mu)*sc + beta, the form the backward pass recomputes u in — not x*sc + (beta - mu*sc), whose two terms are |mean| * rstd large and cancel
+            // (a near-constant channel at |x| ~ 1e4: rstd -> 1/sqrt(eps), both terms ~3e5, y off by 3 % of its range)
+            cst[c] = sc; cst[a.C + c] = muf; cst[2 * a.C + c] = a.beta[c];
             if (blockIdx.x == 0) {
                 if (c == 0 && a.counter) *a.counter += 1;             // nn.BatchNorm2d.num_batches_tracked
                 a.mean[c] = muf; a.rstd[c] = rsf;
@@ -246,11 +288,11 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const BnArgs2 a) {
     for (int g0 = 0; g0 < groups; g0 += gpb) {
         const int gi = g0 + threadIdx.x % gpb, pl = threadIdx.x / gpb;
         if (gi >= groups || pl >= plan) continue;
-        float sc[N], sh[N], ga[N], be[N], mu[N], rs[N], k0[N], k1[N];
+        float sc[N], ga[N], be[N], mu[N], rs[N], k0[N], k1[N];
 #pragma unroll
         for (int j = 0; j < N; ++j) {
             const int c = gi * N + j;
-            if (!BWD) { sc[j] = cst[c]; sh[j] = cst[a.C + c]; }
+            if (!BWD) { sc[j] = cst[c]; mu[j] = cst[a.C + c]; be[j] = cst[2 * a.C + c]; }
             else {
                 mu[j] = cst[c]; rs[j] = cst[a.C + c]; ga[j] = cst[2 * a.C + c]; be[j] = cst[3 * a.C + c]; k0[j] = cst[4 * a.C + c]; k1[j] = cst[5 * a.C + c];
                 sc[j] = rs[j] * ga[j];
@@ -263,7 +305,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const BnArgs2 a) {
             if (!BWD) {
 #pragma unroll
                 for (int j = 0; j < N; ++j) {
-                    float u = __builtin_fmaf((float)xv[j], sc[j], sh[j]);
+                    float u = __builtin_fmaf((float)xv[j] - mu[j], sc[j], be[j]);
                     if (RES) u += (float)rv[j];
                     ov[j] = (T)act_fwd(u, ACT);
                 }
@@ -426,13 +468,15 @@ extern "C" int maf_bn_forward_ex(const void* x, int32_t x_stride, int32_t M, int
     const dim3 gs = stats_grid(M, C, dtype, &lds_s);
     const int ga = bn_grid(M, C, dtype, 8192);
     if (!stats_ready) {                                      // else: the producing kernel has accumulated {sum x, sum x^2} into half `phase` already
+        MAF_REQUIRE(y != x, "bn_forward: y must not alias x (every workgroup of the apply pass re-reads the pivot pixels of x)");
+        a.pivot = 1;                                         // both kernels of this call read the pivot from x itself: no buffer, nothing for the caller to alternate
         if (int rc = det_prepare(a, gs, C, dtype, &lds_s, s)) return rc;
         if (dtype == MAF_F16) hipLaunchKernelGGL((bn_stats_kernel<half_t, false>), gs, dim3(256), lds_s, s, a);
         else hipLaunchKernelGGL((bn_stats_kernel<float, false>), gs, dim3(256), lds_s, s, a);
         det_reduce(a, gs, C, s);
     }
     a.res = residual; a.rs = res_stride;
-    const size_t la = (size_t)2 * C * sizeof(float);
+    const size_t la = (size_t)3 * C * sizeof(float);
 #define MAF_BN_FWD(T_, RES_, ACT_) hipLaunchKernelGGL((bn_apply_kernel<T_, false, RES_, ACT_>), dim3(ga), dim3(256), la, s, a)
 #define MAF_BN_FWD_A(T_, RES_) do { if (act == MAF_ACT_SILU) MAF_BN_FWD(T_, RES_, MAF_ACT_SILU); else if (act == MAF_ACT_RELU) MAF_BN_FWD(T_, RES_, MAF_ACT_RELU); else MAF_BN_FWD(T_, RES_, MAF_ACT_NONE); } while (0)
     if (residual) {

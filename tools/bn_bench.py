@@ -14,7 +14,7 @@ sys.path.insert(0, ROOT)
 import maf_yolo_amd as M                    # noqa: E402
 from maf_yolo_amd import lib, train_ops     # noqa: E402
 
-SHAPES = [(160, 48), (160, 72), (80, 96), (80, 144), (80, 128), (80, 192), (40, 192), (40, 288), (40, 128), (20, 384), (20, 576), (20, 192), (20, 96)]
+SHAPES = [(160, 48), (160, 72), (80, 96), (80, 144), (80, 128), (80, 192), (40, 192), (40, 288), (40, 128), (20, 384), (20, 576), (20, 768), (20, 192), (20, 96)]
 
 
 def main():
