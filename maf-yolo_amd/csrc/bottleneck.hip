@@ -32,7 +32,7 @@
 // the tail's weight fragments (A operand: rows = output channels, permuted so that the four lane groups of a store instruction cover one
 // contiguous 64-byte run of a pixel) arrive by DMA in the LDS the block loop no longer needs.
 #include "maf_common.h"
-#include <type_traits>
+#include "lds_pipe.h"
 
 namespace {
 
@@ -67,20 +67,6 @@ struct BnArgs {
 
 typedef half_t half4v_t __attribute__((ext_vector_type(4)));
 
-template <int N, int I = 0, typename F>
-__device__ __forceinline__ void maf_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        maf_static_for<N, I + 1>(f);
-    }
-}
-
-// LDS reads as inline assembly (the caller counts them and waits with bn_wait_lgkm): see phase B.
-template <int OFF> __device__ __forceinline__ void bn_ds_read_b128(u32x4_t& d, uint32_t addr) { asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF)); }
-template <int OFF> __device__ __forceinline__ void bn_ds_read_b64(u32x2_t& d, uint32_t addr) { asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF)); }
-template <int N> __device__ __forceinline__ void bn_wait_lgkm(u32x4_t& a, u32x2_t& b, u32x2_t& c) { asm volatile("s_waitcnt lgkmcnt(%3)" : "+v"(a), "+v"(b), "+v"(c) : "n"(N)); }
-template <int N> __device__ __forceinline__ void bn_wait_lgkm1(u32x4_t& a) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a) : "n"(N)); }
-template <int N> __device__ __forceinline__ void bn_wait_lgkm2(u32x4_t& a, u32x4_t& b) { asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N)); }
 
 // SiLU of a value that arrives pre-multiplied by log2(e) (pack_bottleneck folds the factor into W1 / b1 / bdw and its inverse into W2):
 // returns log2(e) * silu(x) for the argument log2(e) * x — v_exp_f32 is a base-2 exponential, so no multiplication in front of it.
@@ -182,7 +168,8 @@ __global__ __launch_bounds__(256, ((CT2 == 2 && K <= 5) || (BnCfg<K, S1, CT2>::O
         const int j = seg_stat(my_xcd) + (int)atomicAdd(a.ctr + my_xcd, 1u);
         return j < seg_q + (my_xcd < seg_r ? 1 : 0) ? seg_start(my_xcd) + j : -1;
     };
-    {   // XCD-contiguous tile order: neighbouring tiles (shared halos) run on the same XCD's L2
+    {   // XCD-contiguous tile order: neighbouring tiles (shared halos) run on the same XCD's L2 (maf_xcd_contiguous_id's map, written out: next to
+        // seg_start the call compiles to other code)
         const int bid = blockIdx.x, xcd = bid & 7, j = bid >> 3;
         const int q = a.ntiles >> 3, r = a.ntiles & 7;
         lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
@@ -424,16 +411,16 @@ __global__ __launch_bounds__(256, ((CT2 == 2 && K <= 5) || (BnCfg<K, S1, CT2>::O
                 constexpr int s = t % 8, part = (t / 8) % PARTS, ky = t / (8 * PARTS);
                 constexpr int ot = ((s * K + ky) * PARTS + part) * 256, o = (s * 4 * PS + ky * RWP + part * 4) * 2;
                 static_assert(ot < 65536 && o < 65536, "ds offset field");
-                bn_ds_read_b128<ot>(avr[t % (BD + 1)], a_toe);
+                lp_ds_read_b128<ot>(avr[t % (BD + 1)], a_toe);
                 if constexpr (B128) {
-                    bn_ds_read_b128<o>(bwin[t % (BD + 1)], a_t1l);
+                    lp_ds_read_b128<o>(bwin[t % (BD + 1)], a_t1l);
                 } else {
-                    bn_ds_read_b64<o>(blo[t % (BD + 1)], a_t1l);
-                    bn_ds_read_b64<o>(bhi[t % (BD + 1)], a_t1h);
+                    lp_ds_read_b64<o>(blo[t % (BD + 1)], a_t1l);
+                    lp_ds_read_b64<o>(bhi[t % (BD + 1)], a_t1h);
                 }
             }
         };
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the compiler's own reads (biases) are complete: the counter now counts only the reads below
+        lp_wait_lgkm<0>();   // the compiler's own reads (biases) are complete: the counter now counts only the reads below
         if (!BN_KO(2)) {                                      // KO 2: no phase B
         maf_static_for<BD>([&](auto idx) { ld_step(idx); });
         maf_static_for<NSTEP>([&](auto idx) {
@@ -442,10 +429,10 @@ __global__ __launch_bounds__(256, ((CT2 == 2 && K <= 5) || (BnCfg<K, S1, CT2>::O
             constexpr int ahead = (NSTEP - 1 - t) < BD ? (NSTEP - 1 - t) : BD;      // steps whose reads were issued after step t's
             u32x4_t bw;
             if constexpr (B128) {
-                bn_wait_lgkm2<2 * ahead>(avr[sl], bwin[sl]);
+                lp_wait_lgkm<2 * ahead>(avr[sl], bwin[sl]);
                 bw = bwin[sl];
             } else {
-                bn_wait_lgkm<3 * ahead>(avr[sl], blo[sl], bhi[sl]);
+                lp_wait_lgkm<3 * ahead>(avr[sl], blo[sl], bhi[sl]);
                 bw = (u32x4_t){blo[sl][0], blo[sl][1], bhi[sl][0], bhi[sl][1]};
             }
             const u32x4_t am = Cf::ZT ? avr[sl] : (avr[sl] & toe_mask);
@@ -544,7 +531,7 @@ __global__ __launch_bounds__(256, ((CT2 == 2 && K <= 5) || (BnCfg<K, S1, CT2>::O
                     yf[r][j][q] = (half_t)maf_act<MAF_ACT_SILU>(acc2[r][ct][rr] + b2v[idx]);
                 }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    lp_wait_vm<0>();
     __syncthreads();                                               // the record has landed
     const uint32_t a_w3 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)(smem_raw + lane * 16);
     const f32x4_t* b3l = reinterpret_cast<const f32x4_t*>(smem_raw + NFR * 1024) + g * C3T;
@@ -561,15 +548,15 @@ __global__ __launch_bounds__(256, ((CT2 == 2 && K <= 5) || (BnCfg<K, S1, CT2>::O
             u32x4_t wr[RD + 1];
             auto ld = [&](auto idx) {
                 constexpr int t = decltype(idx)::value;
-                if constexpr (t < NST) bn_ds_read_b128<(FB + t) * 1024>(wr[t % (RD + 1)], a_w3);
+                if constexpr (t < NST) lp_ds_read_b128<(FB + t) * 1024>(wr[t % (RD + 1)], a_w3);
             };
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            lp_wait_lgkm<0>();
             maf_static_for<RD>([&](auto idx) { ld(idx); });
             maf_static_for<NST>([&](auto idx) {
                 constexpr int t = decltype(idx)::value, ks = t / C3T, t3 = t % C3T, sl = t % (RD + 1);
                 ld(std::integral_constant<int, t + RD>{});
                 constexpr int ahead = (NST - 1 - t) < RD ? (NST - 1 - t) : RD;
-                bn_wait_lgkm1<ahead>(wr[sl]);
+                lp_wait_lgkm<ahead>(wr[sl]);
                 const half8_t wv = __builtin_bit_cast(half8_t, wr[sl]);
                 acc3[0][t3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wv, getB(0, ks), acc3[0][t3], 0, 0, 0);
                 acc3[1][t3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wv, getB(1, ks), acc3[1][t3], 0, 0, 0);

@@ -14,6 +14,7 @@
 //                        threshold): a category's segment is split over 120 workgroups, and inside each over the threads in contiguous
 //                        ranges.  Cumulative tp / fp, rc, pr, the right-to-left max envelope, searchsorted(rc, recThrs, 'left').
 #include "maf_common.h"
+#include "block_scan.h"
 
 namespace {
 
@@ -164,39 +165,11 @@ struct AccArgs {
     int64_t n; int32_t I, K, Kp;
 };
 
-struct Cnt3 { int nd, tp, fp; };
-
-// block-wide exclusive scan of three counts, ACC_THREADS threads
-__device__ Cnt3 block_excl_sum3(Cnt3 v, Cnt3* sh) {
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int d = 1; d < ACC_THREADS; d <<= 1) {
-        Cnt3 x = tid >= d ? sh[tid - d] : Cnt3{0, 0, 0};
-        __syncthreads();
-        sh[tid].nd += x.nd; sh[tid].tp += x.tp; sh[tid].fp += x.fp;
-        __syncthreads();
-    }
-    const Cnt3 r{sh[tid].nd - v.nd, sh[tid].tp - v.tp, sh[tid].fp - v.fp};
-    __syncthreads();
-    return r;
-}
-
-// inclusive max over the threads after this one (0 when none), ACC_THREADS threads
-__device__ double block_suffix_max_after(double v, double* sh) {
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int d = 1; d < ACC_THREADS; d <<= 1) {
-        const double x = tid + d < ACC_THREADS ? sh[tid + d] : 0.0;
-        __syncthreads();
-        sh[tid] = fmax(sh[tid], x);
-        __syncthreads();
-    }
-    const double r = tid + 1 < ACC_THREADS ? sh[tid + 1] : 0.0;
-    __syncthreads();
-    return r;
-}
+struct Cnt3 {
+    int nd, tp, fp;
+    __device__ Cnt3& operator+=(const Cnt3& o) { nd += o.nd; tp += o.tp; fp += o.fp; return *this; }
+    __device__ Cnt3 operator-(const Cnt3& o) const { return Cnt3{nd - o.nd, tp - o.tp, fp - o.fp}; }
+};
 
 __device__ __forceinline__ double pr_of(int tp, int fp) { return (double)tp / ((double)fp + (double)tp + EPS); }
 
@@ -217,7 +190,7 @@ __global__ __launch_bounds__(ACC_THREADS) void coco_accumulate_kernel(const AccA
     int cnt = 0;
     if (k >= 0)
         for (int i = tid; i < a.I; i += ACC_THREADS) cnt += a.img_sel[i] ? a.npig[((int64_t)i * a.K + k) * A_ + ar] : 0;
-    const Cnt3 tot0 = block_excl_sum3(Cnt3{cnt, 0, 0}, sh3);
+    const Cnt3 tot0 = block_excl_sum<ACC_THREADS>(Cnt3{cnt, 0, 0}, sh3);
     if (tid == ACC_THREADS - 1) {
         s_npig = tot0.nd + cnt;
         s_s0 = lower_bound(a.keys, a.n, kp);
@@ -257,7 +230,7 @@ __global__ __launch_bounds__(ACC_THREADS) void coco_accumulate_kernel(const AccA
         own.tp += mb & !ib;
         own.fp += !mb & !ib;
     }
-    const Cnt3 pre = block_excl_sum3(own, sh3);
+    const Cnt3 pre = block_excl_sum<ACC_THREADS>(own, sh3);
     if (tid == ACC_THREADS - 1) {
         const int nd = pre.nd + own.nd, tp = pre.tp + own.tp;
         a.recall[(size_t)t * KAM + oqk] = nd ? (double)tp / (double)npig : 0.0;
@@ -274,7 +247,7 @@ __global__ __launch_bounds__(ACC_THREADS) void coco_accumulate_kernel(const AccA
             mx = fmax(mx, pr_of(tp, fp));
         }
     }
-    double env = block_suffix_max_after(mx, shd);
+    double env = block_suffix_max_after<ACC_THREADS>(mx, shd);
     // 3. right to left over the range: the envelope at each position; the positions searchsorted lands on write q / ss
     {
         int nd = pre.nd + own.nd, tp = pre.tp + own.tp, fp = pre.fp + own.fp;

@@ -41,12 +41,7 @@ __global__ __launch_bounds__(256) void conv1dw_kernel(const C1dArgs a) {
     const int OFF_B1 = 2 * a.S1 * 1024, OFF_TOE = OFF_B1 + 128, OFF_BD = OFF_TOE + Cf::NTOE * 16;
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, p = lane & 15;
-    int lid;
-    {
-        const int bid = blockIdx.x, xcd = bid & 7, j = bid >> 3;
-        const int q = a.nwg >> 3, r = a.nwg & 7;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int lid = maf_xcd_contiguous_id(a.nwg);
     const int mb = lid % a.nMB;                              // the mid blocks of a tile run back to back: its X halo stays in L2
     int tt = lid / a.nMB;
     const int tx = tt % a.tilesX; tt /= a.tilesX;

@@ -83,13 +83,10 @@ __global__ __launch_bounds__(256, (9 * CIN * COUT * 2 + (2 * TY + 1) * 33 * ((CI
     };
     // XCD-contiguous tile order (as csrc/stem2.hip): workgroups go to the 8 XCDs round-robin and neighbouring tiles share halo rows / columns — an XCD
     // walks one contiguous eighth of the tiles, so the shared lines are hits in ITS L2
-    int t_first = blockIdx.x, t_end = a.ntiles, t_step = gridDim.x;
-    if ((gridDim.x & 7) == 0 && !(MAF_KO & 128)) {
-        const int xcd = blockIdx.x & 7, q = a.ntiles >> 3, r = a.ntiles & 7, base = xcd * q + min(xcd, r);
-        t_first = base + (int)(blockIdx.x >> 3); t_end = base + q + (xcd < r ? 1 : 0); t_step = gridDim.x >> 3;
-    }
+    const maf_tile_walk_t walk = maf_xcd_contiguous_walk((unsigned)blockIdx.x, (unsigned)gridDim.x, a.ntiles, !(MAF_KO & 128));
+    const int t_first = walk.first, t_end = walk.end, t_step = walk.step;
     if (t_first < t_end) prefetch(t_first);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the DMA pieces of this wave have landed (the barrier below publishes everybody's)
+    lp_wait_vm<0>();             // the DMA pieces of this wave have landed (the barrier below publishes everybody's)
     for (int tile = t_first; tile < t_end; tile += t_step) {
         const int tx = tile % a.tilesX, t2 = tile / a.tilesX, ty = t2 % a.tilesY, b = t2 / a.tilesY;
         const int Y0 = ty * TY, X0 = tx * TX;
@@ -131,19 +128,19 @@ __global__ __launch_bounds__(256, (9 * CIN * COUT * 2 + (2 * TY + 1) * 33 * ((CI
                         asm volatile("ds_read_b64 %0, %1" : "=v"(plo[s_ % (RD + 1)][m]) : "v"(ad));
                         asm volatile("ds_read_b64 %0, %1 offset:8" : "=v"(phi[s_ % (RD + 1)][m]) : "v"(ad));
                     }
-                    lp_static_for<NT>([&](auto tt) {
+                    maf_static_for<NT>([&](auto tt) {
                         constexpr int t = decltype(tt)::value;
                         lp_ds_read_b128<((s_ * NT + t) * 1024) % 65536>(wr[s_ % (RD + 1)][t], wa + ((s_ * NT + t) * 1024) / 65536 * 65536);
                     });
                 }
             };
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            lp_static_for<RD>([&](auto idx) { ld_step(idx); });
-            lp_static_for<KS>([&](auto idx) {
+            lp_wait_lgkm<0>();
+            maf_static_for<RD>([&](auto idx) { ld_step(idx); });
+            maf_static_for<KS>([&](auto idx) {
                 constexpr int s_ = decltype(idx)::value, sl = s_ % (RD + 1);
                 ld_step(std::integral_constant<int, s_ + RD>{});
                 constexpr int ahead = ((KS - 1 - s_) < RD ? (KS - 1 - s_) : RD) * PER;
-                asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(ahead < 15 ? ahead : 15) : "memory");
+                lp_wait_lgkm<(ahead < 15 ? ahead : 15)>();
                 half8_t tf[MR];
 #pragma unroll
                 for (int m = 0; m < MR; ++m) {

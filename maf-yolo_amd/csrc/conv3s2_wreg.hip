@@ -20,6 +20,7 @@
 //     NHWC pixels out as 16-byte pieces after the barrier that also publishes the next patch;
 //   * a twin launch (two convs of one shape: op->aux) gives each conv half of the workgroups.
 #include "maf_common.h"
+#include "lds_pipe.h"
 
 #ifndef MAF_KO
 #define MAF_KO 0            // profiling builds (make ko KO_SRCS=conv3s2_wreg.hip): 128 = plain round-robin tile order
@@ -41,18 +42,6 @@ struct C3wArgs {
 constexpr int W3_TR = 4, W3_TC = 8, W3_SR = 2 * W3_TR + 1, W3_SC = 2 * W3_TC + 1, W3_NPIX = W3_SR * W3_SC;
 constexpr int W3_SLOTS = W3_NPIX * 16;                              // 16-byte slots of a patch image (256 bytes per pixel, whatever Cin)
 
-// LDS reads as inline assembly with hand-counted waits: written as plain loads the compiler issues every fragment read right in front of the MFMA that
-// needs it and waits with lgkmcnt(0) — a full LDS round trip (~130 cycles) per 17-cycle MFMA, 9.4k of the 9.6k cycles a tile took.
-template <int OFF> __device__ __forceinline__ void w3_ds_read_b128(u32x4_t& d, uint32_t addr) { asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF)); }
-template <int N> __device__ __forceinline__ void w3_wait_lgkm(u32x4_t& a) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a) : "n"(N)); }   // "+v": the MFMA that reads `a` cannot move above the wait
-
-template <int N, int I = 0, typename F>
-__device__ __forceinline__ void w3_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        w3_static_for<N, I + 1>(f);
-    }
-}
 
 template <int NW>
 constexpr int w3_patch_bytes() { return (W3_SLOTS + NW * 64 - 1) / (NW * 64) * (NW * 64) * 16; }   // whole DMA rounds: the last one writes past the last pixel
@@ -162,19 +151,17 @@ __global__ __launch_bounds__(NWN * NWM * 64, (NWN * NWM + 3) / 4) void conv3s2_w
     const int act = a.act;
     // XCD-contiguous tile order (as csrc/stem2.hip): workgroups go to the 8 XCDs round-robin and neighbouring tiles share halo rows / columns — an XCD
     // walks one contiguous eighth of a conv's tiles, so the shared lines are hits in ITS L2 (wgc % 8 == 0: the conv's workgroup index keeps blockIdx's XCD)
-    int tile = wg, t_end = a.ntiles, t_step = wgc;
-    if ((wgc & 7) == 0 && !(MAF_KO & 128)) {
-        const int xcd = wg & 7, q = a.ntiles >> 3, r = a.ntiles & 7, base = xcd * q + min(xcd, r);
-        tile = base + (wg >> 3); t_end = base + q + (xcd < r ? 1 : 0); t_step = wgc >> 3;
-    }
+    const maf_tile_walk_t walk = maf_xcd_contiguous_walk(wg, wgc, a.ntiles, !(MAF_KO & 128));
+    int tile = walk.first;
+    const int t_end = walk.end, t_step = walk.step;
     const int t_last = t_end > 0 ? t_end - 1 : 0;
     // NBUF - 1 patches in flight ahead of the one being multiplied (NBUF = 3: a patch has two tile times to arrive)
 #pragma unroll
     for (int k = 0; k < NBUF - 1; ++k)
         if (tile + k * t_step < t_end) dma(tile + k * t_step, k);
         else dma(t_last, k);                                                      // keep the DMA count per wave uniform (the data is never read)
-    if (NBUF == 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ROUNDS) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (NBUF == 3) lp_wait_vm<ROUNDS>();
+    else lp_wait_vm<0>();
     __syncthreads();
     for (int it = 0; tile < t_end; ++it, tile += t_step) {
         const int cur = it % NBUF, ocur = it & 1;
@@ -212,16 +199,16 @@ __global__ __launch_bounds__(NWN * NWM * 64, (NWN * NWM + 3) / 4) void conv3s2_w
                 constexpr int s_ = C1 > 0 ? t % KS : t / MT, m = C1 > 0 ? t / KS : t % MT, tap = s_ / KPT, ky = tap / 3, kx = tap - 3 * ky;
                 constexpr int off = (ky * W3_SC + kx) * 256 + m * (4 * W3_SC * 256);
                 static_assert(off < 65536, "ds offset field");
-                w3_ds_read_b128<off>(fr[t % (RD + 1)], fa[ky >> 1][kx >> 1][s_ % KPT]);
+                lp_ds_read_b128<off>(fr[t % (RD + 1)], fa[ky >> 1][kx >> 1][s_ % KPT]);
             }
         };
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                        // the counter now counts only the reads below
-        w3_static_for<RD>([&](auto idx) { ld_step(idx); });
-        w3_static_for<NSTEP>([&](auto idx) {
+        lp_wait_lgkm<0>();                        // the counter now counts only the reads below
+        maf_static_for<RD>([&](auto idx) { ld_step(idx); });
+        maf_static_for<NSTEP>([&](auto idx) {
             constexpr int t = decltype(idx)::value, s_ = C1 > 0 ? t % KS : t / MT, m = C1 > 0 ? t / KS : t % MT, sl = t % (RD + 1);
             ld_step(std::integral_constant<int, t + RD>{});
             constexpr int ahead = (NSTEP - 1 - t) < RD ? (NSTEP - 1 - t) : RD;
-            w3_wait_lgkm<ahead>(fr[sl]);
+            lp_wait_lgkm<ahead>(fr[sl]);
             const half8_t f = __builtin_bit_cast(half8_t, fr[sl]);
 #pragma unroll
             for (int tt = 0; tt < NTW; ++tt) acc[m][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[s_][tt], f, acc[m][tt], 0, 0, 0);

@@ -24,7 +24,7 @@
 // back-to-back on the same XCD so re-reads of the activations hit that XCD's L2.
 #pragma once
 #include "maf_common.h"
-#include <type_traits>
+#include "lds_pipe.h"
 
 struct ConvArgs {
     const void* src[4];
@@ -119,17 +119,6 @@ template <> struct Frag<float> {
     }
 };
 
-template <int OFF> __device__ __forceinline__ void cm_ds_read_b128(u32x4_t& d, uint32_t addr) { asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF)); }
-template <int N> __device__ __forceinline__ void cm_wait_lgkm(u32x4_t& a) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a) : "n"(N)); }   // "+v": the MFMA that reads `a` stays below the wait
-template <int N> __device__ __forceinline__ void cm_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-template <int N, int I = 0, typename Fn>
-__device__ __forceinline__ void cm_static_for(Fn&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        cm_static_for<N, I + 1>(f);
-    }
-}
 
 template <typename T>
 __device__ __forceinline__ typename Frag<T>::type ldg16(const T* p) {
@@ -463,26 +452,26 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
         };
         const uint32_t lbase = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)(lb_raw + lane * 16);
         const int nstage = (total_steps + KST - 1) / KST;
-        cm_static_for<D>([&](auto j) __attribute__((always_inline)) { issue(decltype(j)::value, j); });
+        maf_static_for<D>([&](auto j) __attribute__((always_inline)) { issue(decltype(j)::value, j); });
         for (int st0 = 0; st0 < nstage; st0 += R) {
-            cm_static_for<R>([&](auto q_tag) __attribute__((always_inline)) {
+            maf_static_for<R>([&](auto q_tag) __attribute__((always_inline)) {
                 constexpr int q = decltype(q_tag)::value;
                 const int st = st0 + q;
                 __builtin_amdgcn_sched_barrier(0);
-                cm_wait_vm<(D - 1) * (FW + KST * PT)>();
+                lp_wait_vm<(D - 1) * (FW + KST * PT)>();
                 __builtin_amdgcn_s_barrier();                             // the bare instruction: __syncthreads() carries a fence that waits for vmcnt(0), i.e. for the whole look-ahead
                 __builtin_amdgcn_sched_barrier(0);
                 issue(st + D, std::integral_constant<int, (q + D) % R>{});
                 __builtin_amdgcn_sched_barrier(0);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the counter now counts only the reads below
+                lp_wait_lgkm<0>();       // the counter now counts only the reads below
                 u32x4_t wr[FR];
-                cm_static_for<FR>([&](auto f_tag) __attribute__((always_inline)) {
+                maf_static_for<FR>([&](auto f_tag) __attribute__((always_inline)) {
                     constexpr int f = decltype(f_tag)::value;
-                    cm_ds_read_b128<(q * FR + f) * 1024>(wr[f], lbase);
+                    lp_ds_read_b128<(q * FR + f) * 1024>(wr[f], lbase);
                 });
-                cm_static_for<FR>([&](auto f_tag) __attribute__((always_inline)) {
+                maf_static_for<FR>([&](auto f_tag) __attribute__((always_inline)) {
                     constexpr int f = decltype(f_tag)::value, u = f / CT, ct = f % CT;
-                    cm_wait_lgkm<FR - 1 - f>(wr[f]);
+                    lp_wait_lgkm<FR - 1 - f>(wr[f]);
                     const frag_t wf = __builtin_bit_cast(frag_t, wr[f]);
 #pragma unroll
                     for (int pt = 0; pt < PT; ++pt) {
@@ -493,7 +482,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
                 __builtin_amdgcn_sched_barrier(0);
             });
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // the look-ahead stages past the end (clamped re-reads) are still landing
+        lp_wait_vm<0>();                  // the look-ahead stages past the end (clamped re-reads) are still landing
     } else if constexpr (LB) {
         // Long reductions (3x3 taps, wide concats): the four waves of a workgroup use the SAME weight fragments, and at
         // CT KiB per k-step per wave the L2 -> L1 weight stream, not HBM, bounds the layer.  Here the workgroup fetches each

@@ -5,19 +5,6 @@
 
 namespace {
 
-// LDS reads of the weight fragments as inline assembly with hand-counted waits: as plain loads the compiler reads two fragments into the same two
-// register quads right in front of the two MFMAs that need them and waits with lgkmcnt(1) / lgkmcnt(0) — a full LDS round trip (~130 cycles) per
-// pair of 17-cycle MFMAs, 4.7k cycles for the 72 MFMAs of a 288 -> 128 tile instead of 1.2k.
-template <int OFF> __device__ __forceinline__ void sl_ds_read_b128(u32x4_t& d, uint32_t addr) { asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF)); }
-template <int N> __device__ __forceinline__ void sl_wait_lgkm(u32x4_t& a) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a) : "n"(N)); }   // "+v": the MFMA that reads `a` cannot move above the wait
-
-template <int N, int I = 0, typename F>
-__device__ __forceinline__ void sl_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        sl_static_for<N, I + 1>(f);
-    }
-}
 
 template <int ACT, int CT>
 __device__ __forceinline__ void sl_store(const f32x4_t (&acc)[CT], int r, half_t* op, int nvalid) {
@@ -207,15 +194,15 @@ __global__ __launch_bounds__(NW * 64) void conv1x1_stream_lds_kernel(const ConvA
             u32x4_t wr[RD + 1];
             auto ld_step = [&](auto idx) {
                 constexpr int s_ = decltype(idx)::value;
-                if constexpr (s_ < NSTEP) sl_ds_read_b128<(s_ * 1024) % 65536>(wr[s_ % (RD + 1)], wbase[(s_ * 1024) / 65536]);
+                if constexpr (s_ < NSTEP) lp_ds_read_b128<(s_ * 1024) % 65536>(wr[s_ % (RD + 1)], wbase[(s_ * 1024) / 65536]);
             };
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // the counter now counts only the reads below
-            sl_static_for<RD>([&](auto idx) { ld_step(idx); });
-            sl_static_for<NSTEP>([&](auto idx) {
+            lp_wait_lgkm<0>();          // the counter now counts only the reads below
+            maf_static_for<RD>([&](auto idx) { ld_step(idx); });
+            maf_static_for<NSTEP>([&](auto idx) {
                 constexpr int s_ = decltype(idx)::value, ks = s_ / CT, ct = s_ % CT, sl = s_ % (RD + 1);
                 ld_step(std::integral_constant<int, s_ + RD>{});
                 constexpr int ahead = (NSTEP - 1 - s_) < RD ? (NSTEP - 1 - s_) : RD;
-                sl_wait_lgkm<ahead>(wr[sl]);
+                lp_wait_lgkm<ahead>(wr[sl]);
                 acc[ct] = F::mma(af[ks], __builtin_bit_cast(frag_t, wr[sl]), acc[ct]);
                 __builtin_amdgcn_sched_barrier(0);                      // keep the issue order as written
             });
@@ -283,7 +270,7 @@ __global__ __launch_bounds__(NW * 64) void conv1x1_stream_lds_kernel(const ConvA
     int t = wg * NW + wave;
     const bool any = t < ntiles;
     if (any) load_tile(t, fa);                                           // in flight beside the weight DMA
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                     // this wave's DMA pieces have landed ...
+    lp_wait_vm<0>();                     // this wave's DMA pieces have landed ...
     __syncthreads();                                                     // ... and everybody else's
     if constexpr (ST) {
         frag_t fb2[KS];

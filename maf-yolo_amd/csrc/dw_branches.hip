@@ -8,9 +8,9 @@
 //   forward   x is staged ONCE (halo of K0), the NB filters walk the same LDS tile, NB outputs                (1 + NB passes instead of 2 NB)
 //   dgrad     dx = sum_j corr(dz_j, flip(w_j)): the branches' dz_j are staged one after the other, the sum stays in registers (fp32) and is
 //             written once                                                                                    (NB + 1 passes instead of 5 NB - 3)
-// Same tile scheme as dwconv.hip (2-D tile x channel block per workgroup, 4-pixel strips per lane, v_fma_mix_f32); the weight gradients stay
+// Same tile scheme as dwconv.hip (2-D tile x channel block per workgroup, 4-pixel strips per lane, the vmac of dw_vmac.h); the weight gradients stay
 // per branch (train_ops.hip: dw_wgrad_kernel on the weight-gradient stream).
-#include "maf_common.h"
+#include "dw_vmac.h"
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -32,26 +32,6 @@ template <typename T> struct Vec;
 template <> struct Vec<half_t> { static constexpr int N = 8; typedef half8_t type; };
 template <> struct Vec<float> { static constexpr int N = 4; typedef f32x4_t type; };
 
-__device__ __forceinline__ void vmac(float (&acc)[8], const half8_t& v, const half8_t& w) {
-    const u32x4_t a = __builtin_bit_cast(u32x4_t, v), b = __builtin_bit_cast(u32x4_t, w);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[1,1,0]" : "+v"(acc[2 * q]) : "v"(a[q]), "v"(b[q]));
-        asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,1,0]" : "+v"(acc[2 * q + 1]) : "v"(a[q]), "v"(b[q]));
-    }
-}
-__device__ __forceinline__ void vmac(float (&acc)[4], const f32x4_t& v, const f32x4_t& w) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] = __builtin_fmaf(v[j], w[j], acc[j]);
-}
-
-template <int N, int I = 0, typename F>
-__device__ __forceinline__ void db_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        db_static_for<N, I + 1>(f);
-    }
-}
 
 // kernel size of branch J of a block whose large kernel is K0 (common.py:2997-3008): 3 -> 3, 3, 1;  5 -> 5, 3, 1;  7 -> 7, 5, 3;  9 -> 9, 7, 5, 3
 template <int K0, int J> constexpr int branch_k() { return K0 == 3 ? (J < 2 ? 3 : 1) : K0 - 2 * J; }
@@ -81,12 +61,7 @@ __device__ __forceinline__ void strip_mac(float (&acc)[R][Vec<T>::N], const type
 struct TileId { int b, y0, x0, c0, cbe; };
 
 __device__ __forceinline__ TileId decode_tile(const DwbArgs& a) {
-    int lid;                                                    // XCD-aware bijective remap (as dwconv.hip): logical tiles contiguous per XCD
-    {
-        const int bid = blockIdx.x, xcd = bid & 7, j = bid >> 3;
-        const int q = a.nwg >> 3, r = a.nwg & 7;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int lid = maf_xcd_contiguous_id(a.nwg);
     TileId t;
     const int cb = lid % a.nCB;
     int u = lid / a.nCB;
@@ -144,7 +119,7 @@ __global__ __launch_bounds__(256) void dwb_fwd_kernel(const DwbArgs a) {
     const int RW = a.TW + K0 - 1;
     vec_t* wl = tile + (a.TH + K0 - 1) * RW * PS;              // [NB][K0 * K0 * CG]
     stage_tile<T, K0>(tile, static_cast<const T*>(a.src[0]), a.src_stride[0], a, t, CGB, PS);
-    db_static_for<NB>([&](auto jc) {
+    maf_static_for<NB>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
         stage_weights<T, branch_k<K0, j>()>(wl + j * K0 * K0 * CG, static_cast<const T*>(a.w[j]), a, t, CGB);
     });
@@ -164,7 +139,7 @@ __global__ __launch_bounds__(256) void dwb_fwd_kernel(const DwbArgs a) {
         const int cgi = it % CGB, u = it / CGB, s = u % NSX, ry = u / NSX;
         const int oy = t.y0 + ry, ox0 = t.x0 + s * R;
         const bool live = it0 + (int)threadIdx.x < items && oy < a.H && ox0 < a.W;
-        db_static_for<NB>([&](auto jc) {
+        maf_static_for<NB>([&](auto jc) {
             constexpr int j = decltype(jc)::value, K = branch_k<K0, j>(), off = P0 - K / 2;
             float acc[R][N];
 #pragma unroll
@@ -237,7 +212,7 @@ __global__ __launch_bounds__(256) void dwb_dgrad_kernel(const DwbArgs a) {
 #pragma unroll
             for (int q = 0; q < N; ++q) acc[sl][r][q] = 0.f;
     }
-    db_static_for<NB>([&](auto jc) {
+    maf_static_for<NB>([&](auto jc) {
         constexpr int j = decltype(jc)::value, K = branch_k<K0, j>();
         if constexpr (j > 0) __syncthreads();                  // everybody has finished reading the previous branch's tile
         stage_tile<T, K>(tile, static_cast<const T*>(a.src[j]), a.src_stride[j], a, t, CGB, PS);

@@ -19,7 +19,7 @@
 // Pixel stride in LDS is padded by 32 bytes so the strips of a wave land on different bank groups.
 // blockIdx is remapped so that consecutive logical tiles (channel blocks of the same pixels, then
 // x-neighbours) run on the same XCD and share its L2.
-#include "maf_common.h"
+#include "dw_vmac.h"
 
 namespace {
 
@@ -43,21 +43,6 @@ template <> struct Vec<float> {
     typedef f32x4_t type;
 };
 
-// acc[j] += v[j] * w[j] over one 16-byte vector, fp32 accumulate.  For f16 this is v_fma_mix_f32 (f16 sources read
-// straight from the packed registers, no v_cvt and no fp32 copies => ~100 fewer VGPRs than cvt + v_pk_fma_f32).
-__device__ __forceinline__ void vmac(float (&acc)[8], const half8_t& v, const half8_t& w) {
-    const u32x4_t a = __builtin_bit_cast(u32x4_t, v), b = __builtin_bit_cast(u32x4_t, w);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[1,1,0]" : "+v"(acc[2 * q]) : "v"(a[q]), "v"(b[q]));
-        asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,1,0]" : "+v"(acc[2 * q + 1]) : "v"(a[q]), "v"(b[q]));
-    }
-}
-__device__ __forceinline__ void vmac(float (&acc)[4], const f32x4_t& v, const f32x4_t& w) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] = __builtin_fmaf(v[j], w[j], acc[j]);
-}
-
 template <typename T, int K, int ACT>
 __global__ __launch_bounds__(256) void dwconv_tile_kernel(const DwArgs a) {
     constexpr int N = Vec<T>::N;
@@ -66,13 +51,7 @@ __global__ __launch_bounds__(256) void dwconv_tile_kernel(const DwArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     vec_t* tile = reinterpret_cast<vec_t*>(smem_raw);
 
-    // XCD-aware bijective remap: logical tile ids are contiguous per XCD (block b runs on XCD b % 8)
-    int lid;
-    {
-        const int bid = blockIdx.x, xcd = bid & 7, j = bid >> 3;
-        const int q = a.nwg >> 3, r = a.nwg & 7;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int lid = maf_xcd_contiguous_id(a.nwg);
     const int cb = lid % a.nCB;
     int t = lid / a.nCB;
     const int tx = t % a.tilesX; t /= a.tilesX;

@@ -55,12 +55,7 @@ __global__ __launch_bounds__(256) void dwconv_dot2_kernel(const Dw2Args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char d2_raw[];
     u32x4_t* tile = reinterpret_cast<u32x4_t*>(d2_raw);                  // [RH][PWP][NQ] pair vectors (+ pad per pair)
 
-    int lid;                                                             // XCD-aware bijective remap (as dwconv.hip)
-    {
-        const int bid = blockIdx.x, xcd = bid & 7, j = bid >> 3;
-        const int q = a.nwg >> 3, r = a.nwg & 7;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int lid = maf_xcd_contiguous_id(a.nwg);
     const int cb = lid % a.nCB;
     int t = lid / a.nCB;
     const int tx = t % a.tilesX; t /= a.tilesX;

@@ -15,6 +15,7 @@
 #include <type_traits>
 #include <utility>
 #include "maf_common.h"
+#include "lds_pipe.h"
 
 namespace {
 
@@ -28,17 +29,6 @@ struct DwmArgs {
 
 typedef half_t half4v_t __attribute__((ext_vector_type(4)));
 
-template <int N, int I = 0, typename F>
-__device__ __forceinline__ void dwm_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        dwm_static_for<N, I + 1>(f);
-    }
-}
-// LDS reads as inline assembly: the caller counts them and waits with dwm_wait_lgkm
-template <int OFF> __device__ __forceinline__ void dwm_ds_read_b128(u32x4_t& d, uint32_t addr) { asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF)); }
-template <int OFF> __device__ __forceinline__ void dwm_ds_read_b64(u32x2_t& d, uint32_t addr) { asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF)); }
-template <int N> __device__ __forceinline__ void dwm_wait_lgkm(u32x4_t& a, u32x2_t& b, u32x2_t& c) { asm volatile("s_waitcnt lgkmcnt(%3)" : "+v"(a), "+v"(b), "+v"(c) : "n"(N)); }
 
 template <int K>
 struct DwmCfg {
@@ -60,12 +50,7 @@ __global__ __launch_bounds__(256) void dwconv_mfma_kernel(const DwmArgs a) {
     half8_t* toe = reinterpret_cast<half8_t*>(smem_raw + 32 * Cf::PSB);
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, p = lane & 15;
-    int lid;
-    {
-        const int bid = blockIdx.x, xcd = bid & 7, j = bid >> 3;
-        const int q = a.nwg >> 3, r = a.nwg & 7;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int lid = maf_xcd_contiguous_id(a.nwg);
     const int cb = lid % a.nCB;                              // the channel blocks of a tile run back to back (shared halo lines in L2)
     int tt = lid / a.nCB;
     const int tx = tt % a.tilesX; tt /= a.tilesX;
@@ -115,18 +100,18 @@ __global__ __launch_bounds__(256) void dwconv_mfma_kernel(const DwmArgs a) {
             constexpr int s = t % 8, part = (t / 8) % PARTS, ky = t / (8 * PARTS);
             constexpr int ot = ((s * K + ky) * PARTS + part) * 256, o = (s * 4 * PS + ky * RWP + part * 4) * 2;
             static_assert(ot < 65536 && o < 65536, "ds offset field");
-            dwm_ds_read_b128<ot>(avr[t % (BD + 1)], a_toe);
-            dwm_ds_read_b64<o>(blo[t % (BD + 1)], a_t1l);
-            dwm_ds_read_b64<o>(bhi[t % (BD + 1)], a_t1h);
+            lp_ds_read_b128<ot>(avr[t % (BD + 1)], a_toe);
+            lp_ds_read_b64<o>(blo[t % (BD + 1)], a_t1l);
+            lp_ds_read_b64<o>(bhi[t % (BD + 1)], a_t1h);
         }
     };
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the counter now counts only the reads below
-    dwm_static_for<BD>([&](auto idx) { ld_step(idx); });
-    dwm_static_for<NSTEP>([&](auto idx) {
+    lp_wait_lgkm<0>();       // the counter now counts only the reads below
+    maf_static_for<BD>([&](auto idx) { ld_step(idx); });
+    maf_static_for<NSTEP>([&](auto idx) {
         constexpr int t = decltype(idx)::value, s = t % 8, sl = t % (BD + 1);
         ld_step(std::integral_constant<int, t + BD>{});
         constexpr int ahead = (NSTEP - 1 - t) < BD ? (NSTEP - 1 - t) : BD;          // steps whose reads were issued after step t's
-        dwm_wait_lgkm<3 * ahead>(avr[sl], blo[sl], bhi[sl]);
+        lp_wait_lgkm<3 * ahead>(avr[sl], blo[sl], bhi[sl]);
         const u32x4_t bw = (u32x4_t){blo[sl][0], blo[sl][1], bhi[sl][0], bhi[sl][1]};
         const u32x4_t am = avr[sl] & toe_mask;
         dacc[s] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_t, am), __builtin_bit_cast(half8_t, bw), dacc[s], 0, 0, 0);

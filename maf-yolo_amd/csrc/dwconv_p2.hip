@@ -70,12 +70,7 @@ __global__ __launch_bounds__(512) void dwconv_p2_kernel(const Dp2Args a) {
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int nw = blockDim.x >> 6;
 
-    int lid;                                                             // XCD-aware bijective remap (as dwconv.hip)
-    {
-        const int bid = blockIdx.x, xcd = bid & 7, j = bid >> 3;
-        const int q = a.nwg >> 3, r = a.nwg & 7;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int lid = maf_xcd_contiguous_id(a.nwg);
     const int unit = lid * nw + wv;                                      // one wave = one (image, tile, input channel group); channel groups fastest
     if (unit >= a.nunits) return;                                        // no barrier below unless STG (then nunits % nw == 0: nobody leaves)
     uint32_t t_ = (uint32_t)unit, q_;
@@ -106,11 +101,11 @@ __global__ __launch_bounds__(512) void dwconv_p2_kernel(const Dp2Args a) {
     }
     const int nstrips = a.TH * a.SPR;
     const uint32_t row_step = (uint32_t)a.PITCH * 16, sub_bytes = (uint32_t)a.sub_slots * 16;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    lp_wait_vm<0>();
 
     half8_t hold[STG ? NF : 1][R];
     int hold_s = 0;
-    lp_static_for<(STG ? NF : 1)>([&](auto fidx) {
+    maf_static_for<(STG ? NF : 1)>([&](auto fidx) {
     constexpr int FI = decltype(fidx)::value;
 #pragma unroll 1
     for (int f = FI; f < (STG ? FI + 1 : a.nf); ++f) {
@@ -152,7 +147,7 @@ __global__ __launch_bounds__(512) void dwconv_p2_kernel(const Dp2Args a) {
                     }
                 };
                 load_step(std::integral_constant<int, 0>{});
-                lp_static_for<NS>([&](auto idx) {
+                maf_static_for<NS>([&](auto idx) {
                     constexpr int s_ = decltype(idx)::value, bf = s_ & 1, h = s_ & 1;
                     if constexpr (s_ + 1 < NS) load_step(std::integral_constant<int, s_ + 1>{});
                     __builtin_amdgcn_sched_barrier(0);
@@ -194,7 +189,7 @@ __global__ __launch_bounds__(512) void dwconv_p2_kernel(const Dp2Args a) {
         const int cg0 = cgi - wv;                                        // the workgroup's first channel group (cgi % nw == wv)
         const int npieces = nstrips * R * nw;
         half_t* obase = a.out + a.out_coff + (size_t)b * a.H * a.W * a.out_stride;
-        lp_static_for<NF>([&](auto fidx) {
+        maf_static_for<NF>([&](auto fidx) {
             constexpr int FI = decltype(fidx)::value;
             __syncthreads();                                             // every wave has left its planes (FI = 0) / read the previous filter's runs back
             if (lane < nstrips) {

@@ -24,13 +24,6 @@
 
 namespace {
 
-template <int N, int I = 0, typename F>
-__device__ __forceinline__ void ht_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        ht_static_for<N, I + 1>(f);
-    }
-}
 
 constexpr int NT2 = 5;                 // 80 output columns of the second GEMM (80 classes; 68 DFL logits + zero padding)
 constexpr int NO = 85, NC = 80, NR = 68;
@@ -124,7 +117,7 @@ __global__ __launch_bounds__(256, C <= 128 ? 2 : 1) void head_tail_kernel(const 
     const int unit0 = blockIdx.x * 4 + wave;
     load_x(unit0);
     if constexpr (WLDS) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        lp_wait_vm<0>();
         __syncthreads();
     }
     float bias2[NT2];
@@ -149,9 +142,9 @@ __global__ __launch_bounds__(256, C <= 128 ? 2 : 1) void head_tail_kernel(const 
                 constexpr int s_ = decltype(idx)::value;
                 if constexpr (s_ < NSTEP) lp_ds_read_b128<(s_ * 1024) % 65536>(wr[s_ % (RD + 1)], w1a[(s_ * 1024) / 65536]);
             };
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            lp_static_for<RD>([&](auto idx) { ld_step(idx); });
-            lp_static_for<NSTEP>([&](auto idx) {
+            lp_wait_lgkm<0>();
+            maf_static_for<RD>([&](auto idx) { ld_step(idx); });
+            maf_static_for<NSTEP>([&](auto idx) {
                 constexpr int s_ = decltype(idx)::value, t = s_ / KS, ks = s_ % KS, sl = s_ % (RD + 1);
                 ld_step(std::integral_constant<int, s_ + RD>{});
                 constexpr int ahead = (NSTEP - 1 - s_) < RD ? (NSTEP - 1 - s_) : RD;
@@ -165,7 +158,7 @@ __global__ __launch_bounds__(256, C <= 128 ? 2 : 1) void head_tail_kernel(const 
             // the record does not fit the LDS: its T1 + NT2 chunks (the fragments of one 16-channel tile: KS KiB) pass through two LDS
             // buffers — chunk c + 1 travels global -> registers -> LDS while chunk c is multiplied, one barrier per chunk
             f32x4_t even[PT];
-            ht_static_for<T1>([&](auto idx) {
+            maf_static_for<T1>([&](auto idx) {
                 constexpr int t = decltype(idx)::value;
                 uint4 nxt[CHV];
                 chunk_load(t + 1, nxt);
@@ -225,9 +218,9 @@ __global__ __launch_bounds__(256, C <= 128 ? 2 : 1) void head_tail_kernel(const 
                 constexpr int s_ = decltype(idx)::value;
                 if constexpr (s_ < NSTEP) lp_ds_read_b128<(s_ * 1024) % 65536>(wr[s_ % (RD + 1)], w2a[(s_ * 1024) / 65536]);
             };
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            lp_static_for<RD>([&](auto idx) { ld_step(idx); });
-            lp_static_for<NSTEP>([&](auto idx) {
+            lp_wait_lgkm<0>();
+            maf_static_for<RD>([&](auto idx) { ld_step(idx); });
+            maf_static_for<NSTEP>([&](auto idx) {
                 constexpr int s_ = decltype(idx)::value, t = s_ / KS, j = s_ % KS, sl = s_ % (RD + 1);
                 ld_step(std::integral_constant<int, s_ + RD>{});
                 constexpr int ahead = (NSTEP - 1 - s_) < RD ? (NSTEP - 1 - s_) : RD;
@@ -238,7 +231,7 @@ __global__ __launch_bounds__(256, C <= 128 ? 2 : 1) void head_tail_kernel(const 
                 __builtin_amdgcn_sched_barrier(0);
             });
         } else {
-            ht_static_for<NT2>([&](auto idx) {
+            maf_static_for<NT2>([&](auto idx) {
                 constexpr int t = decltype(idx)::value, c = T1 + t;
                 uint4 nxt[CHV];
                 chunk_load(c + 1 < NCH ? c + 1 : 0, nxt);                       // after the last chunk: chunk 0 again, for the next unit

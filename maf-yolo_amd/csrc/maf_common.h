@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 #include "../../include/mafyolo_hip.h"
 
 typedef _Float16 half_t;
@@ -55,6 +56,38 @@ __device__ __forceinline__ float maf_act_rt(float x, int act) {
         case MAF_ACT_SIGMOID: return __builtin_amdgcn_rcpf(1.f + __expf(-x));
         default: return x;
     }
+}
+
+// f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N - 1>{}): a loop whose index is a constant expression in the body
+// (template arguments, `if constexpr`, asm "n" operands), unrolled by construction
+template <int N, int I = 0, typename F>
+__device__ __forceinline__ void maf_static_for(F&& f) {
+    if constexpr (I < N) {
+        f(std::integral_constant<int, I>{});
+        maf_static_for<N, I + 1>(f);
+    }
+}
+
+// Workgroups go to the 8 XCDs round-robin by block id (block b runs on XCD b % 8), and neighbouring tiles share lines (halos, the channel
+// blocks of one tile) that should be fetched into ONE XCD's L2.  Both helpers make the logical tile ids of an XCD contiguous.
+//
+// One tile per workgroup: the bijective map block id -> logical id of a grid of nwg blocks (the first nwg % 8 XCDs own one id more).
+__device__ __forceinline__ int maf_xcd_contiguous_id(int nwg) {
+    const int bid = blockIdx.x, xcd = bid & 7, j = bid >> 3;
+    const int q = nwg >> 3, r = nwg & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
+}
+// Persistent workgroups: workgroup wg of nwg walks `for (t = first; t < end; t += step)`, a contiguous eighth of the tiles shared with the
+// other workgroups of its XCD.  Needs nwg % 8 == 0 (wg & 7 is then the XCD); otherwise, or with contiguous = false, plain round-robin.
+struct maf_tile_walk_t { int first, end, step; };
+template <typename I>
+__device__ __forceinline__ maf_tile_walk_t maf_xcd_contiguous_walk(I wg, I nwg, int ntiles, bool contiguous = true) {
+    maf_tile_walk_t w = {(int)wg, ntiles, (int)nwg};
+    if ((nwg & 7) == 0 && contiguous) {
+        const int xcd = wg & 7, q = ntiles >> 3, r = ntiles & 7, base = xcd * q + min(xcd, r);
+        w.first = base + (int)(wg >> 3); w.end = base + q + (xcd < r ? 1 : 0); w.step = nwg >> 3;
+    }
+    return w;
 }
 
 static inline int maf_cdiv(int a, int b) { return (a + b - 1) / b; }

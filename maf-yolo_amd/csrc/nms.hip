@@ -19,6 +19,7 @@
 // IEEE division and no FMA contraction (this file is compiled with -ffp-contract=off), and the
 // quotient is compared with the threshold in double as torchvision's CPU kernel does.
 #include "maf_common.h"
+#include "lds_pipe.h"
 #include <cmath>
 #include <cstring>
 
@@ -384,7 +385,7 @@ __device__ __forceinline__ void nms_select_body(const NmsArgs& a, const int b) {
             c.score = __uint_as_float(~(unsigned int)(key >> 32)); c.flat = flat;
             lst = by_class ? cls : 0;
             c.pad = (unsigned int)lst;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            lp_wait_vm<0>();
             t_ld += __builtin_readcyclecounter() - ta0;
             const int p1 = cstart[lst + 1];
             for (int p = cstart[lst]; p < p1 && alive; p += 4) {           // 4 independent LDS gathers per step

@@ -12,6 +12,7 @@
 //                  precision envelope of each (class, threshold) segment, np.interp at the 1000 + 101 grid points, the trapezoid AP;
 //                  then the summary.  Three stream-ordered launches.
 #include "maf_common.h"
+#include "block_scan.h"
 #include "scale_coords.h"
 
 namespace {
@@ -266,36 +267,6 @@ __device__ double np_sum(const double* v, int n, int stride) {
 __device__ __forceinline__ double px_at(int k) { return k == 999 ? 1.0 : (double)k * (1.0 / 999.0); }
 __device__ __forceinline__ double x101_at(int k) { return k == 100 ? 1.0 : (double)k * (1.0 / 100.0); }
 
-// block-wide exclusive scan (sum) / inclusive suffix max of one value per thread, CURVE_THREADS threads
-__device__ int block_excl_sum(int v, int* sh) {
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int d = 1; d < CURVE_THREADS; d <<= 1) {
-        const int t = tid >= d ? sh[tid - d] : 0;
-        __syncthreads();
-        sh[tid] += t;
-        __syncthreads();
-    }
-    const int r = sh[tid] - v;
-    __syncthreads();
-    return r;
-}
-__device__ double block_suffix_max_after(double v, double* sh) {
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int d = 1; d < CURVE_THREADS; d <<= 1) {
-        const double t = tid + d < CURVE_THREADS ? sh[tid + d] : 0.0;
-        __syncthreads();
-        sh[tid] = fmax(sh[tid], t);
-        __syncthreads();
-    }
-    const double r = tid + 1 < CURVE_THREADS ? sh[tid + 1] : 0.0;
-    __syncthreads();
-    return r;
-}
-
 // one workgroup per (class, threshold): the segment of class c in the sorted records
 __global__ __launch_bounds__(CURVE_THREADS) void pr_curves_kernel(const CurveArgs a) {
     __shared__ int shi[CURVE_THREADS];
@@ -326,7 +297,7 @@ __global__ __launch_bounds__(CURVE_THREADS) void pr_curves_kernel(const CurveArg
     // tp count of this thread's chunk -> its starting cumulative sum
     int cnt = 0;
     for (int64_t i = i0; i < i1; ++i) cnt += (a.masks[a.perm[s + i]] >> j) & 1;
-    int tpc = block_excl_sum(cnt, shi);
+    int tpc = block_excl_sum<CURVE_THREADS>(cnt, shi);
     double cmax = 0.0;
     for (int64_t i = i0; i < i1; ++i) {
         tpc += (a.masks[a.perm[s + i]] >> j) & 1;
@@ -334,7 +305,7 @@ __global__ __launch_bounds__(CURVE_THREADS) void pr_curves_kernel(const CurveArg
         cmax = fmax(cmax, (double)tpc / (double)(i + 1));
     }
     // precision envelope: suffix maximum (the trailing 0 of compute_ap never wins: precision >= 0)
-    double run = block_suffix_max_after(cmax, shd);
+    double run = block_suffix_max_after<CURVE_THREADS>(cmax, shd);
     for (int64_t i = i1 - 1; i >= i0; --i) {
         run = fmax(run, (double)T[i] / (double)(i + 1));
         E[i] = run;

@@ -123,11 +123,8 @@ __global__ __launch_bounds__(256, C0 > 32 ? 1 : TY == 8 ? 2 : 3) void stem2_kern
     // XCD-contiguous tile order: workgroups go to the 8 XCDs round-robin, and a tile shares the 128-byte lines of its left halo column and its
     // three halo rows with its neighbours — an XCD walks ONE contiguous eighth of the tiles, its resident workgroups a window of consecutive
     // tiles (several tile rows), so those lines are hits in that XCD's L2 instead of a second fetch through another one
-    int t_first = blockIdx.x, t_end = a.ntiles, t_step = gridDim.x;
-    if ((gridDim.x & 7) == 0 && !(MAF_KO & 128)) {
-        const int xcd = blockIdx.x & 7, q = a.ntiles >> 3, r = a.ntiles & 7, base = xcd * q + min(xcd, r);
-        t_first = base + (int)(blockIdx.x >> 3); t_end = base + q + (xcd < r ? 1 : 0); t_step = gridDim.x >> 3;
-    }
+    const maf_tile_walk_t walk = maf_xcd_contiguous_walk((unsigned)blockIdx.x, (unsigned)gridDim.x, a.ntiles, !(MAF_KO & 128));
+    const int t_first = walk.first, t_end = walk.end, t_step = walk.step;
     if (t_first < t_end) prefetch(t_first);
     for (int tile = t_first; tile < t_end; tile += t_step) {
         const int tx = tile % a.tilesX, t2 = tile / a.tilesX, ty = t2 % a.tilesY, b = t2 / a.tilesY;
