@@ -701,6 +701,53 @@ int maf_mosaic_affine(const maf_augment_sample_t* samples, const maf_augment_sam
                       maf_stream_t stream);
 
 /*
+ * copy_paste on polygon labels (yolov6/data/data_augment.py:285-307), opt-in through TrainAugment(polygons=True) in maf-yolo_amd/augment.py.
+ *
+ * maf_polygon_mask: for each of n masks, the union of what cv2.drawContours(im_new, [contour], -1, (1, 1, 1), cv2.FILLED) draws for that
+ * mask's contours on a C x C canvas, as a bit mask; all masks in one launch.  The fill rule (OpenCV's fillPoly with line_type 8, shift 0:
+ * every edge as LineIterator's 8-connected clipped line, plus the even-odd scan-line interior in 16.16 fixed point) is the one restated in
+ * tests/copy_paste_ref.py, bit for bit.
+ *   table         HOST int32 table (validated before anything touches the device); table_dev: DEVICE copy of the same table (4-byte
+ *                 aligned), read by the kernel.  Three arrays back to back:
+ *                   mask_start [n + 1]       mask i owns contours [mask_start[i], mask_start[i + 1]); rises from 0 to npoly; a mask may own none
+ *                   poly_start [npoly + 1]   contour p owns vertices [poly_start[p], poly_start[p + 1]); rises strictly from 0 to nvert
+ *                   xy [2 nvert]             x, y of every vertex, each within [-MAF_POLYGON_COORD_MAX, MAF_POLYGON_COORD_MAX]; vertices may
+ *                                            lie outside the canvas, the kernel clips
+ *   n, npoly, nvert   1..MAF_POLYGON_MAX_MASKS masks, 0..MAF_POLYGON_MAX_CONTOURS contours, 0..MAF_POLYGON_MAX_VERTICES vertices in all
+ *   C             the canvas side, 1..MAF_POLYGON_MAX_CANVAS
+ *   masks         DEVICE, 4-byte aligned, uint32 [n, C, W], W = (C + 31) / 32: pixel (x, y) of mask i is bit x & 31 of word
+ *                 (i C + y) W + (x >> 5); the padding bits of a row's last word are 0.  Every word is written exactly once (plain stores,
+ *                 no memset needed), a mask without contours as zeros.
+ */
+#define MAF_POLYGON_COORD_MAX 32767
+#define MAF_POLYGON_MAX_CANVAS 16384
+#define MAF_POLYGON_MAX_MASKS 65535
+#define MAF_POLYGON_MAX_CONTOURS (1 << 24)
+#define MAF_POLYGON_MAX_VERTICES (1 << 26)
+int maf_polygon_mask(const int32_t* table, const int32_t* table_dev, int32_t n, int32_t npoly, int32_t nvert, int32_t C, uint32_t* masks,
+                     maf_stream_t stream);
+
+/*
+ * maf_mosaic_affine_paste: maf_mosaic_affine with copy_paste's pixels, im[flip(im_new) != 0] = flip(im)[...], applied to the virtual canvas
+ * before the warp.  Same samples table, same checks, same output contract (uint8 [B, 3, S, S], every byte written exactly once); a second
+ * table gives every sample its masks:
+ *   paste [B]     HOST table (validated before anything touches the device); paste_dev: DEVICE copy of the same table, read by the kernel
+ *   mask[l]       layer l's mask in maf_polygon_mask's layout for canvas side C (DEVICE, 4-byte aligned), or NULL: nothing pasted in that
+ *                 layer.  A mask needs its layer (ntiles[l] > 0) and tile rectangles inside [0, C]^2.
+ *   C             the canvas side; must be 2 S
+ * Each of warpAffine's four taps at canvas (x, y) inside [0, C)^2 reads canvas (C-1-x, y) when bit (C-1-x, y) of the layer's mask is set,
+ * else canvas (x, y); outside [0, C)^2 it reads 114.  A table without any mask gives maf_mosaic_affine's bytes.
+ * maf_augment_paste_size: sizeof(maf_augment_paste_t), for bindings to check their mirror.
+ */
+typedef struct {
+    const uint32_t* mask[2];
+    int32_t C, reserved;
+} maf_augment_paste_t;
+int32_t maf_augment_paste_size(void);
+int maf_mosaic_affine_paste(const maf_augment_sample_t* samples, const maf_augment_sample_t* samples_dev, const maf_augment_paste_t* paste,
+                            const maf_augment_paste_t* paste_dev, int32_t B, int32_t S, uint8_t* out, maf_stream_t stream);
+
+/*
  * maf_resize_area: load_image's cv2.resize INTER_AREA of an evaluation frame larger than the load size (yolov6/data/datasets.py:277-300 with
  * r < 1 and augment off), n frames in one launch, uint8 HWC in, uint8 HWC out.  Both axes shrink or stay (new_w <= w, new_h <= h); the pixel
  * rule is OpenCV's as restated in tests/area_ref.py, bit for bit.  The caller (maf-yolo_amd/letterbox.py) picks the path of every frame with

@@ -10,9 +10,15 @@ images with few labels, augment_hsv and the flips follow (yolov6/data/data_augme
                            and ONE launch of maf_mosaic_affine write the uint8 [B, 3, s, s] batch; the [N, 6] targets go up in one
                            non-blocking copy.  No device -> host synchronisation.
 
-Scope.  Box labels only: with no polygon segments the reference's copy_paste and mask_refine do nothing and draw nothing (copy_paste only
-calls random.sample when a segment exists), so neither appears here; polygon segments raise MafError.  `mixup > 1` reaches a call with the
-wrong signature in the reference (mixup(self, ..., type="simple")) and raises MafError.  albument, rect training and the per-worker RNG
+Scope.  Box labels by default: with no polygon segments the reference's copy_paste and mask_refine do nothing and draw nothing (copy_paste
+only calls random.sample when a segment exists), and polygon segments raise MafError.  TrainAugment(..., segments, polygons=True) takes
+YOLO-segment labels (one polygon per label row): copy_paste (data_augment.py:285-307) then picks objects with random.sample in the
+reference's order, appends their mirrored boxes and polygons and records the int32 contours it hands to cv2.drawContours (Layer.paste);
+random_affine(mask_refine=True) warps every polygon resampled to 1000 points and boxes it with segment2box.  On the device the contours
+become one bit mask per layer (csrc/polygon_mask.hip maf_polygon_mask, OpenCV's FILLED rule as restated in tests/copy_paste_ref.py) and
+maf_mosaic_affine_paste reads canvas (C-1-x, y) instead of (x, y) where the mask is set at (C-1-x, y), C = 2s.  The reference indexes
+segments by label row and misindexes on datasets that mix box and polygon rows; here every image needs one polygon per row, or none.
+`mixup > 1` reaches a call with the wrong signature in the reference (mixup(self, ..., type="simple")) and raises MafError.  albument, rect training and the per-worker RNG
 streams of a multi-worker DataLoader are out of scope; frames arrive decoded, as uint8 HWC (BGR, cv2.imread order) CUDA tensors.
 
 Labels keep the dtype the dataset gives them (TrainValDataset.labels are float32 arrays): every step below runs the reference's NumPy
@@ -56,6 +62,7 @@ class Layer:
     M: np.ndarray
     s: float
     center: tuple = None        # mosaic centre (xc, yc); None in the non-mosaic branch
+    paste: list = field(default_factory=list)   # copy_paste: the int32 [k, 2] contours handed to cv2.drawContours(FILLED), in order
 
 
 @dataclass
@@ -111,13 +118,16 @@ class TrainAugment:
     shapes  per image (h0, w0), the decoded frame's size
     hyp     the reference's data_aug dict (configs/MAF-YOLO-n.py:31-47): hsv_h/s/v, degrees, translate, scale, shear, flipud, fliplr,
             mosaic, mixup, dy_label, dy_mixup, copy_paste, mask_refine
-    segments  optional per-image polygon lists; any non-empty one raises MafError (box labels only)
+    segments  optional per-image polygon lists.  polygons=False (the default): any non-empty one raises MafError (box labels only).
+              polygons=True: segments[i] is a list of float [k, 2] arrays (normalised xy), one per row of labels[i] (an empty list for an
+              image without labels), as the reference's label reader builds them from YOLO-segment files (datasets.py:746-749); draw then
+              runs copy_paste and mask_refine as the reference does and Layer.paste holds the pasted contours
 
     draw(index) consumes `random` and `np.random` in the reference's order and returns a Sample.  The dynamic-mixup cache of
     get_cache_mosaic (max 20 entries, oldest popped, refilled with 3 random images while it holds <= 4) lives in the object, as it lives
     in the dataset: draws of one object form one stream."""
 
-    def __init__(self, labels, shapes, hyp, img_size=640, segments=None):
+    def __init__(self, labels, shapes, hyp, img_size=640, segments=None, polygons=False):
         self.labels = list(labels)
         self.shapes = [(int(h), int(w)) for h, w in shapes]
         if len(self.labels) != len(self.shapes) or not self.labels:
@@ -125,8 +135,24 @@ class TrainAugment:
         for lab in self.labels:
             if lab.ndim != 2 or lab.shape[1] != 5:
                 raise MafError("TrainAugment: labels are [n, 5] (cls, x, y, w, h) box arrays; polygon labels are not supported")
-        if segments is not None and any(len(s) for s in segments):
-            raise MafError("TrainAugment: polygon segments are not supported (box labels only: copy_paste / mask_refine need segments)")
+        self.polygons = bool(polygons)
+        if not self.polygons:
+            if segments is not None and any(len(s) for s in segments):
+                raise MafError("TrainAugment: polygon segments are not supported without polygons=True (box labels only: copy_paste / "
+                               "mask_refine need segments)")
+            self.segments = [[] for _ in self.labels]
+        else:
+            segments = [[] for _ in self.labels] if segments is None else [[np.asarray(x) for x in s] for s in segments]
+            if len(segments) != len(self.labels):
+                raise MafError("TrainAugment: one polygon list per image")
+            for i, (lab, segs) in enumerate(zip(self.labels, segments)):
+                if len(segs) != len(lab):
+                    raise MafError("TrainAugment: image %d has %d polygons for %d label rows (polygons=True needs one polygon per row; "
+                                   "datasets that mix box and polygon rows are not supported)" % (i, len(segs), len(lab)))
+                for x in segs:
+                    if x.ndim != 2 or x.shape[1] != 2 or not len(x) or x.dtype.kind != "f":
+                        raise MafError("TrainAugment: a polygon is a float [k, 2] array of normalised xy with k >= 1")
+            self.segments = segments
         self.hyp = dict(hyp)
         for k in ("test_load_size", "letterbox_return_int"):
             if k in self.hyp:
@@ -154,7 +180,7 @@ class TrainAugment:
         if random.random() < hyp["mosaic"]:
             idx = [index] + random.choices(range(0, len(self)), k=3)
             random.shuffle(idx)
-            layer, labels = self._mosaic([(i, self.loaded_hw(i), self.labels[i]) for i in idx])
+            layer, labels = self._mosaic([(i, self.loaded_hw(i), self.labels[i], self.segments[i]) for i in idx])
             sample = Sample(index, True, [layer])
             if random.random() < hyp["mixup"]:
                 sample.labels = self._mixup(sample, labels, random.randint(0, len(self) - 1))
@@ -204,23 +230,23 @@ class TrainAugment:
 
     def _cache_mosaic(self, index):
         """get_cache_mosaic (datasets.py:522-575): append, refill (<= 4) or pop the oldest (> 20), then the newest + 3 random entries."""
-        self.cache.append((index, self.loaded_hw(index), self.labels[index]))
+        self.cache.append((index, self.loaded_hw(index), self.labels[index], self.segments[index]))
         if len(self.cache) <= 4:
             idx = random.choices(range(0, len(self)), k=3)
             random.shuffle(idx)
             for i in idx:
-                self.cache.append((i, self.loaded_hw(i), self.labels[i]))
+                self.cache.append((i, self.loaded_hw(i), self.labels[i], self.segments[i]))
         elif len(self.cache) > MAX_CACHED_IMAGES:
             self.cache.pop(0)
         picks = [-1] + random.choices(range(0, len(self.cache) - 1), k=3)
         return self._mosaic([self.cache[p] for p in picks])
 
     def _mosaic(self, items):
-        """mosaic_augmentation (data_augment.py:225-276) on (index, (h, w), labels) x 4 -> (Layer, labels after random_affine)."""
+        """mosaic_augmentation (data_augment.py:190-254) on (index, (h, w), labels, polygons) x 4 -> (Layer, labels after random_affine)."""
         s = self.img_size
         yc, xc = (int(random.uniform(s // 2, 3 * s // 2)) for _ in range(2))
-        tiles, labels4 = [], []
-        for k, (i, (h, w), lab) in enumerate(items):
+        tiles, labels4, segment4 = [], [], []
+        for k, (i, (h, w), lab, segs) in enumerate(items):
             if k == 0:
                 x1a, y1a, x2a, y2a = max(xc - w, 0), max(yc - h, 0), xc, yc
                 x1b, y1b = w - (x2a - x1a), h - (y2a - y1a)
@@ -243,13 +269,19 @@ class TrainAugment:
                 boxes[:, 2] = w * (lab[:, 1] + lab[:, 3] / 2) + padw
                 boxes[:, 3] = h * (lab[:, 2] + lab[:, 4] / 2) + padh
                 lab[:, 1:] = boxes
+                segs = [_xyn2xy(x, w, h, padw, padh) for x in segs]
             labels4.append(lab)
+            segment4.extend(segs)
         labels4 = np.concatenate(labels4, 0)
-        np.clip(labels4[:, 1:], 0, 2 * s, out=labels4[:, 1:])
-        M, sc, labels4 = self._affine((2 * s, 2 * s), labels4)
+        for x in (labels4[:, 1:], *segment4):
+            np.clip(x, 0, 2 * s, out=x)
+        paste = []
+        if self.polygons and self.hyp["copy_paste"]:
+            labels4, paste = _copy_paste(2 * s, labels4, segment4, self.hyp["copy_paste"])
+        M, sc, labels4 = self._affine((2 * s, 2 * s), labels4, segment4)
         if not (M != np.eye(3)).any():
             raise MafError("TrainAugment: an identity transform on a mosaic (translate >= 0.5) returns the 2s canvas in the reference")
-        return Layer(tiles, M, sc, (xc, yc)), labels4
+        return Layer(tiles, M, sc, (xc, yc), paste), labels4
 
     def _letterboxed(self, index):
         """The non-mosaic branch (datasets.py:194-237): load_image -> letterbox(auto=False, scaleup=True) -> random_affine."""
@@ -275,9 +307,10 @@ class TrainAugment:
         sample.labels = labels
         return sample
 
-    def _affine(self, img_hw, labels):
-        """get_transform_matrix + random_affine's box path (data_augment.py:108-187): six uniform draws, corners -> min / max, clip to the
-        output, box_candidates -> (M, s, labels)."""
+    def _affine(self, img_hw, labels, segments=()):
+        """get_transform_matrix + random_affine (data_augment.py:111-187): six uniform draws; boxes from the corners -> min / max, clipped to
+        the output, or, with polygons and mask_refine, from every polygon resampled to 1000 points, warped and boxed by segment2box; then
+        box_candidates -> (M, s, labels)."""
         hyp, s = self.hyp, self.img_size
         height = width = s
         C = np.eye(3)
@@ -295,7 +328,14 @@ class TrainAugment:
         T[1, 2] = random.uniform(0.5 - hyp["translate"], 0.5 + hyp["translate"]) * height
         M = T @ S @ R @ C
         n = len(labels)
-        if n:
+        if n and any(x.any() for x in segments) and hyp["mask_refine"]:
+            new = np.zeros((n, 4))
+            for i, segment in enumerate(_resample_segments(segments)):
+                xy = np.ones((len(segment), 3))
+                xy[:, :2] = segment
+                xy = xy @ M.T
+                new[i] = _segment2box(xy[:, :2], width, height)
+        elif n:
             xy = np.ones((n * 4, 3))
             xy[:, :2] = labels[:, [1, 2, 3, 4, 1, 4, 3, 2]].reshape(n * 4, 2)       # corners x1y1, x2y2, x1y2, x2y1
             xy = (xy @ M.T)[:, :2].reshape(n, 8)
@@ -303,10 +343,69 @@ class TrainAugment:
             new = np.concatenate((x.min(1), y.min(1), x.max(1), y.max(1))).reshape(4, n).T
             new[:, [0, 2]] = new[:, [0, 2]].clip(0, width)
             new[:, [1, 3]] = new[:, [1, 3]].clip(0, height)
+        if n:
             keep = _box_candidates(labels[:, 1:5].T * sc, new.T)
             labels = labels[keep]
             labels[:, 1:5] = new[keep]
         return M, sc, labels
+
+
+def _xyn2xy(x, w, h, padw, padh):
+    """xyn2xy (data_augment.py:279-284): a normalised polygon to canvas pixels, in the polygon's dtype."""
+    y = np.copy(x)
+    y[..., 0] = w * x[..., 0] + padw
+    y[..., 1] = h * x[..., 1] + padh
+    return y
+
+
+def _bbox_ioa(box1, box2, eps=1e-7):
+    """bbox_ioa (data_augment.py:308-327): intersection over the area of box2, [n, m]."""
+    b1_x1, b1_y1, b1_x2, b1_y2 = box1.T
+    b2_x1, b2_y1, b2_x2, b2_y2 = box2.T
+    inter_area = (np.minimum(b1_x2[:, None], b2_x2) - np.maximum(b1_x1[:, None], b2_x1)).clip(0) * \
+                 (np.minimum(b1_y2[:, None], b2_y2) - np.maximum(b1_y1[:, None], b2_y1)).clip(0)
+    box2_area = (b2_x2 - b2_x1) * (b2_y2 - b2_y1) + eps
+    return inter_area / box2_area
+
+
+def _copy_paste(w, labels, segments, p):
+    """copy_paste (data_augment.py:285-307) without the pixels: the objects whose mirror image overlaps every object by < 30 % are
+    candidates, random.sample picks round(p n) of them (Python's round: half to even); each pick appends its mirrored label row and
+    polygon (to `segments`, in place) and is drawn UNMIRRORED, truncated to int32 -> (labels, the contours in drawing order).
+    w: the canvas width (2s), a Python int as im.shape gives it."""
+    paste = []
+    n = len(segments)
+    if p and n:
+        boxes = np.stack([w - labels[:, 3], labels[:, 2], w - labels[:, 1], labels[:, 4]], axis=-1)
+        ioa = _bbox_ioa(boxes, labels[:, 1:5])
+        indexes = np.nonzero((ioa < 0.30).all(1))[0]
+        n = len(indexes)
+        for j in random.sample(list(indexes), k=round(p * n)):
+            l, box, s = labels[j], boxes[j], segments[j]
+            labels = np.concatenate((labels, [[l[0], *box]]), 0)
+            segments.append(np.concatenate((w - s[:, 0:1], s[:, 1:2]), 1))
+            paste.append(segments[j].astype(np.int32))
+    return labels, paste
+
+
+def _resample_segments(segments, n=1000):
+    """resample_segments (data_augment.py:328-335): every closed polygon to n points by linear interpolation over the vertex index."""
+    out = []
+    for s in segments:
+        s = np.concatenate((s, s[0:1, :]), axis=0)
+        x = np.linspace(0, len(s) - 1, n)
+        xp = np.arange(len(s))
+        out.append(np.concatenate([np.interp(x, xp, s[:, i]) for i in range(2)]).reshape(2, -1).T)
+    return out
+
+
+def _segment2box(segment, width, height):
+    """segment2box (data_augment.py:336-341): the box of the points inside the image; np.zeros((1, 4)) when no inside point has a
+    nonzero x (Python's any(x) on the x coordinates, as the reference writes it)."""
+    x, y = segment.T
+    inside = (x >= 0) & (y >= 0) & (x <= width) & (y <= height)
+    x, y, = x[inside], y[inside]
+    return np.array([x.min(), y.min(), x.max(), y.max()]) if any(x) else np.zeros((1, 4))
 
 
 def _box_candidates(box1, box2, wh_thr=2, ar_thr=20, area_thr=0.1, eps=1e-16):
@@ -353,13 +452,19 @@ def train_batch(frames, indices, aug):
     aug      the TrainAugment holding the labels, hyp and the dynamic-mixup cache
 
     Two launches: the load_image resizes of every distinct frame the batch reads (plus letterbox's second resize where the non-mosaic branch
-    takes one) into one staging buffer, then maf_mosaic_affine.  Tables and targets go up from pinned memory: no device -> host sync."""
+    takes one) into one staging buffer, then maf_mosaic_affine.  Tables and targets go up from pinned memory: no device -> host sync.
+    When copy_paste pasted something in any layer of the batch (TrainAugment(polygons=True)), the contours go up with the sample table, one
+    maf_polygon_mask launch draws every pasted layer's mask and maf_mosaic_affine_paste takes maf_mosaic_affine's place."""
     from . import torch_ops
     samples = [i if isinstance(i, Sample) else aug.draw(int(i)) for i in indices]
     if not samples:
         raise MafError("train_batch: no indices")
     host, dev, keep = stage_batch(frames, samples, aug)
-    imgs = torch_ops.load().mosaic_affine(host, _upload(host.numpy(), dev), aug.img_size)
+    paste = stage_paste(samples)
+    if paste is None:
+        imgs = torch_ops.load().mosaic_affine(host, _upload(host.numpy(), dev), aug.img_size)
+    else:
+        imgs = _mosaic_affine_paste(host, paste, dev, aug.img_size)
     del keep                                                   # staging and resize tables: stream-ordered frees, after the launch
     n = sum(len(smp.labels) for smp in samples)
     targets = np.zeros((n, 6), np.float32)
@@ -370,6 +475,50 @@ def train_batch(frames, indices, aug):
         targets[row:row + k, 1:] = smp.labels
         row += k
     return imgs, _upload(targets, dev)
+
+
+def stage_paste(samples):
+    """The contours copy_paste drew for a batch -> None when no layer has any, else (the int32 table of maf_polygon_mask: mask_start |
+    poly_start | xy, (n, npoly, nvert), [(sample, layer)] of each mask): one mask per layer with pasted contours."""
+    slots = [(b, l) for b, smp in enumerate(samples) for l, layer in enumerate(smp.layers) if layer.paste]
+    if not slots:
+        return None
+    polys = [np.ascontiguousarray(c, np.int32).reshape(-1, 2) for b, l in slots for c in samples[b].layers[l].paste]
+    for c in polys:
+        if not len(c) or np.abs(c).max() > lib.POLYGON_COORD_MAX:
+            raise MafError("train_batch: a pasted contour needs a vertex, and coordinates within +-%d" % lib.POLYGON_COORD_MAX)
+    mask_start = np.cumsum([0] + [len(samples[b].layers[l].paste) for b, l in slots])
+    poly_start = np.cumsum([0] + [len(c) for c in polys])
+    table = np.concatenate([mask_start, poly_start, np.concatenate(polys, 0).reshape(-1)]).astype(np.int32)
+    return table, (len(slots), len(polys), int(poly_start[-1])), slots
+
+
+def _mosaic_affine_paste(host, paste, dev, s):
+    """maf_polygon_mask + maf_mosaic_affine_paste for a staged batch (host: stage_batch's sample table, paste: stage_paste's result).  The
+    masks come from the caching allocator (the kernel writes every word: no memset); the sample table, the paste table and the contours go
+    up in ONE copy from pinned memory."""
+    from . import torch_ops
+    table, (n, npoly, nvert), slots = paste
+    B, side = host.shape[0], 2 * s
+    words = side * ((side + 31) // 32)
+    masks = torch.empty((n, words), dtype=torch.int32, device=dev)
+    ptab = (lib.MafAugmentPaste * B)()
+    for e in ptab:
+        e.C = side
+    for i, (b, l) in enumerate(slots):
+        ptab[b].mask[l] = masks.data_ptr() + 4 * words * i
+    parts = [host.numpy().reshape(-1), np.frombuffer(ptab, np.uint8), table.view(np.uint8)]
+    offs = np.cumsum([0] + [(len(p) + 7) // 8 * 8 for p in parts])          # every part 8-byte aligned in the upload
+    buf = np.zeros(int(offs[-1]), np.uint8)
+    for o, p in zip(offs, parts):
+        buf[o:o + len(p)] = p
+    up = _upload(buf, dev)
+    samples_dev, paste_dev, table_dev = (up[o:o + len(p)] for o, p in zip(offs, parts))
+    st = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):                               # the C-ABI launches on the current device: the frames' one
+        lib.check(lib.load().maf_polygon_mask(table.ctypes.data, table_dev.data_ptr(), n, npoly, nvert, side, masks.data_ptr(), st))
+    paste_host = torch.from_numpy(parts[1].reshape(B, -1).copy())
+    return torch_ops.load().mosaic_affine_paste(host, samples_dev.view(B, -1), paste_host, paste_dev.view(B, -1), s)
 
 
 def stage_batch(frames, samples, aug):

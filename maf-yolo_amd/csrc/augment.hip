@@ -16,6 +16,11 @@
 // The canvas is never materialised: each of the 4 taps of a pixel is looked up in the <= 4 tile rectangles of its layer (sample
 // parameters are workgroup-uniform: scalar loads).  Every output byte is written exactly once; every frame read is inside the frame
 // (the host checks each tile's rectangle + offset against the frame before the launch).
+//
+// copy_paste (maf_mosaic_affine_paste, PASTE = true in the shared device code): a layer may carry the bit mask maf_polygon_mask
+// (polygon_mask.hip) drew for its pasted contours; a tap at canvas (x, y) inside [0, C)^2 then reads canvas (C-1-x, y) where bit (C-1-x, y)
+// is set: im[flip(im_new) != 0] = flip(im)[...] of data_augment.py:303-305 without a second canvas.  One 32-bit mask load per tap, from
+// the C^2 / 8 bytes of the layer's mask.
 #include "maf_common.h"
 #include "resize_linear.h"
 
@@ -79,18 +84,39 @@ __device__ __forceinline__ void canvas_px(const maf_augment_tile_t* __restrict__
     b = g = r = GREY;
 }
 
-// warpAffine INTER_LINEAR of one layer at output pixel (px, py) -> BGR
-__device__ __forceinline__ void warp_px(const double* __restrict__ m, const maf_augment_tile_t* __restrict__ t, int nt, int px, int py, int* bgr) {
+// canvas_px after copy_paste: inside [0, C)^2 the mirrored pixel where the mask is set there; outside, 114
+__device__ __forceinline__ void pasted_px(const maf_augment_tile_t* __restrict__ t, int nt, const uint32_t* __restrict__ mask, int C, int cx, int cy,
+                                          int& b, int& g, int& r) {
+    if ((unsigned)cx >= (unsigned)C || (unsigned)cy >= (unsigned)C) {
+        b = g = r = GREY;
+        return;
+    }
+    const int mx = C - 1 - cx;
+    if ((mask[(size_t)cy * (C >> 5) + (mx >> 5)] >> (mx & 31)) & 1u) cx = mx;
+    canvas_px(t, nt, cx, cy, b, g, r);
+}
+
+// warpAffine INTER_LINEAR of one layer at output pixel (px, py) -> BGR; PASTE: the layer's copy_paste mask (may be null) over a C x C canvas
+template <bool PASTE>
+__device__ __forceinline__ void warp_px(const double* __restrict__ m, const maf_augment_tile_t* __restrict__ t, int nt, const uint32_t* __restrict__ mask,
+                                        int C, int px, int py, int* bgr) {
     const int X = ((int)rint((m[1] * py + m[2]) * 1024.0) + 16 + (int)rint(m[0] * px * 1024.0)) >> 5;
     const int Y = ((int)rint((m[4] * py + m[5]) * 1024.0) + 16 + (int)rint(m[3] * px * 1024.0)) >> 5;
     const int sx = min(max(X >> 5, -32768), 32767), sy = min(max(Y >> 5, -32768), 32767);
     const int fx = X & 31, fy = Y & 31;
     const int w0 = (32 - fx) * (32 - fy) * 32, w1 = fx * (32 - fy) * 32, w2 = (32 - fx) * fy * 32, w3 = fx * fy * 32;
     int v[4][3];
-    canvas_px(t, nt, sx, sy, v[0][0], v[0][1], v[0][2]);
-    canvas_px(t, nt, sx + 1, sy, v[1][0], v[1][1], v[1][2]);
-    canvas_px(t, nt, sx, sy + 1, v[2][0], v[2][1], v[2][2]);
-    canvas_px(t, nt, sx + 1, sy + 1, v[3][0], v[3][1], v[3][2]);
+    if (PASTE && mask) {                                        // workgroup-uniform
+        pasted_px(t, nt, mask, C, sx, sy, v[0][0], v[0][1], v[0][2]);
+        pasted_px(t, nt, mask, C, sx + 1, sy, v[1][0], v[1][1], v[1][2]);
+        pasted_px(t, nt, mask, C, sx, sy + 1, v[2][0], v[2][1], v[2][2]);
+        pasted_px(t, nt, mask, C, sx + 1, sy + 1, v[3][0], v[3][1], v[3][2]);
+    } else {
+        canvas_px(t, nt, sx, sy, v[0][0], v[0][1], v[0][2]);
+        canvas_px(t, nt, sx + 1, sy, v[1][0], v[1][1], v[1][2]);
+        canvas_px(t, nt, sx, sy + 1, v[2][0], v[2][1], v[2][2]);
+        canvas_px(t, nt, sx + 1, sy + 1, v[3][0], v[3][1], v[3][2]);
+    }
     for (int c = 0; c < 3; ++c) bgr[c] = (v[0][c] * w0 + v[1][c] * w1 + v[2][c] * w2 + v[3][c] * w3 + (1 << 14)) >> 15;
 }
 
@@ -131,7 +157,9 @@ __device__ __forceinline__ void hsv_px(int* bgr, const int* sdiv, const int* hdi
     bgr[0] = round_u8(ob); bgr[1] = round_u8(og); bgr[2] = round_u8(orr);
 }
 
-__global__ __launch_bounds__(THREADS) void mosaic_affine_kernel(const maf_augment_sample_t* __restrict__ samples, int S, uint8_t* __restrict__ out) {
+template <bool PASTE>
+__device__ __forceinline__ void mosaic_affine_body(const maf_augment_sample_t* __restrict__ samples, const maf_augment_paste_t* __restrict__ paste, int S,
+                                                   uint8_t* __restrict__ out) {
     __shared__ int sdiv[256], hdiv[256];
     __shared__ uint8_t lut[768];
     const int b = blockIdx.y;
@@ -146,6 +174,9 @@ __global__ __launch_bounds__(THREADS) void mosaic_affine_kernel(const maf_augmen
     }
     __syncthreads();
     const int nt0 = sm->ntiles[0], nt1 = sm->ntiles[1];
+    const uint32_t* mask0 = PASTE ? paste[b].mask[0] : nullptr;
+    const uint32_t* mask1 = PASTE ? paste[b].mask[1] : nullptr;
+    const int C = PASTE ? paste[b].C : 0;
     const int flipud = sm->flipud, fliplr = sm->fliplr;
     const double r = sm->r, r1 = 1.0 - r;
     const int nq = S >> 2;
@@ -158,10 +189,10 @@ __global__ __launch_bounds__(THREADS) void mosaic_affine_kernel(const maf_augmen
         for (int j = 0; j < 4; ++j) {
             const int px = fliplr ? S - 1 - (x4 + j) : x4 + j;
             int bgr[3];
-            warp_px(sm->minv[0], sm->tile[0], nt0, px, py, bgr);
+            warp_px<PASTE>(sm->minv[0], sm->tile[0], nt0, mask0, C, px, py, bgr);
             if (nt1) {
                 int o2[3];
-                warp_px(sm->minv[1], sm->tile[1], nt1, px, py, o2);
+                warp_px<PASTE>(sm->minv[1], sm->tile[1], nt1, mask1, C, px, py, o2);
                 for (int c = 0; c < 3; ++c) bgr[c] = (int)((double)bgr[c] * r + (double)o2[c] * r1);
             }
             if (hsv) hsv_px(bgr, sdiv, hdiv, lut);
@@ -171,8 +202,18 @@ __global__ __launch_bounds__(THREADS) void mosaic_affine_kernel(const maf_augmen
     }
 }
 
+__global__ __launch_bounds__(THREADS) void mosaic_affine_kernel(const maf_augment_sample_t* __restrict__ samples, int S, uint8_t* __restrict__ out) {
+    mosaic_affine_body<false>(samples, nullptr, S, out);
+}
+
+__global__ __launch_bounds__(THREADS) void mosaic_affine_paste_kernel(const maf_augment_sample_t* __restrict__ samples,
+                                                                      const maf_augment_paste_t* __restrict__ paste, int S, uint8_t* __restrict__ out) {
+    mosaic_affine_body<true>(samples, paste, S, out);
+}
+
 }  // namespace
 
+extern "C" int32_t maf_augment_paste_size(void) { return (int32_t)sizeof(maf_augment_paste_t); }
 extern "C" int32_t maf_augment_sample_size(void) { return (int32_t)sizeof(maf_augment_sample_t); }
 
 extern "C" int maf_augment_resize(const maf_augment_frame_t* frames, const maf_augment_frame_t* frames_dev, int32_t n, maf_stream_t stream) {
@@ -191,8 +232,8 @@ extern "C" int maf_augment_resize(const maf_augment_frame_t* frames, const maf_a
     return maf_check_hip(hipGetLastError(), "augment_resize launch");
 }
 
-extern "C" int maf_mosaic_affine(const maf_augment_sample_t* samples, const maf_augment_sample_t* samples_dev, int32_t B, int32_t S, uint8_t* out,
-                                 maf_stream_t stream) {
+// the checks of maf_mosaic_affine's arguments, shared with maf_mosaic_affine_paste
+static int check_mosaic_affine(const maf_augment_sample_t* samples, const maf_augment_sample_t* samples_dev, int32_t B, int32_t S, uint8_t* out) {
     MAF_REQUIRE(samples && samples_dev && out, "mosaic_affine: null pointer (host table, its device copy, out)");
     MAF_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, "mosaic_affine: out must be 4-byte aligned (32-bit stores)");
     MAF_REQUIRE(B > 0, "mosaic_affine: B must be positive");
@@ -213,6 +254,35 @@ extern "C" int maf_mosaic_affine(const maf_augment_sample_t* samples, const maf_
                             "mosaic_affine: a tile rectangle reads outside its frame");
             }
     }
+    return 0;
+}
+
+extern "C" int maf_mosaic_affine(const maf_augment_sample_t* samples, const maf_augment_sample_t* samples_dev, int32_t B, int32_t S, uint8_t* out,
+                                 maf_stream_t stream) {
+    if (int rc = check_mosaic_affine(samples, samples_dev, B, S, out)) return rc;
     hipLaunchKernelGGL(mosaic_affine_kernel, dim3(S / MA_ROWS, B), dim3(THREADS), 0, static_cast<hipStream_t>(stream), samples_dev, (int)S, out);
     return maf_check_hip(hipGetLastError(), "mosaic_affine launch");
+}
+
+extern "C" int maf_mosaic_affine_paste(const maf_augment_sample_t* samples, const maf_augment_sample_t* samples_dev, const maf_augment_paste_t* paste,
+                                       const maf_augment_paste_t* paste_dev, int32_t B, int32_t S, uint8_t* out, maf_stream_t stream) {
+    MAF_REQUIRE(paste && paste_dev, "mosaic_affine_paste: null pointer (host paste table, its device copy)");
+    if (int rc = check_mosaic_affine(samples, samples_dev, B, S, out)) return rc;
+    MAF_REQUIRE((reinterpret_cast<uintptr_t>(paste_dev) & 7) == 0, "mosaic_affine_paste: paste_dev must be 8-byte aligned");
+    for (int i = 0; i < B; ++i) {
+        const maf_augment_paste_t& p = paste[i];
+        MAF_REQUIRE(p.C == 2 * S, "mosaic_affine_paste: the canvas side C must be 2 S");
+        for (int l = 0; l < 2; ++l) {
+            if (!p.mask[l]) continue;
+            MAF_REQUIRE((reinterpret_cast<uintptr_t>(p.mask[l]) & 3) == 0, "mosaic_affine_paste: a mask must be 4-byte aligned");
+            MAF_REQUIRE(samples[i].ntiles[l] > 0, "mosaic_affine_paste: a mask for a layer without tiles");
+            for (int k = 0; k < samples[i].ntiles[l]; ++k) {
+                const maf_augment_tile_t& t = samples[i].tile[l][k];
+                MAF_REQUIRE(t.x0 >= 0 && t.y0 >= 0 && t.x1 <= p.C && t.y1 <= p.C, "mosaic_affine_paste: a tile of a pasted layer leaves the C x C canvas");
+            }
+        }
+    }
+    hipLaunchKernelGGL(mosaic_affine_paste_kernel, dim3(S / MA_ROWS, B), dim3(THREADS), 0, static_cast<hipStream_t>(stream), samples_dev, paste_dev,
+                       (int)S, out);
+    return maf_check_hip(hipGetLastError(), "mosaic_affine_paste launch");
 }

@@ -9,6 +9,8 @@
 //   rows, counts = torch.ops.mafyolo.decode_nms(pred, conf, iou, agnostic, multi_label, max_det, classes)   # non_max_suppression (yolov6/utils/nms.py:31-105)
 //   imgs = torch.ops.mafyolo.letterbox(frames, H, W, geometry, color, bgr)   # letterbox + precess_image (data_augment.py:53-82, inferer.py:169-179)
 //   imgs = torch.ops.mafyolo.mosaic_affine(samples, samples_dev, S)     # mosaic + random_affine + mixup + augment_hsv + flips (datasets.py:147-275)
+//   masks = torch.ops.mafyolo.polygon_mask(table, table_dev, n, npoly, nvert, C)            # cv2.drawContours(FILLED) of copy_paste (data_augment.py:301)
+//   imgs = torch.ops.mafyolo.mosaic_affine_paste(samples, samples_dev, paste, paste_dev, S) # ... with copy_paste's pixels (data_augment.py:303-305)
 //   torch.ops.mafyolo.pr_match(rows, count, targets, img, H, W, iouv, nc, flags, cm_conf, cm_iou, offs, i, keys, masks, state)  # evaler.py:195-238
 //   out = torch.ops.mafyolo.pr_curves(keys, masks, state, nc, niou)    # ap_per_class + the summary of evaler.py:240-268 (metrics.py:13-103)
 //   img, cat, box, score = torch.ops.mafyolo.coco_append(packed, total, img_index, cat_lut)          # COCOeval results (evaler.py:299-300)
@@ -422,6 +424,45 @@ Tensor mosaic_affine(const Tensor& samples, const Tensor& samples_dev, int64_t S
     return out;
 }
 
+// table: CPU int32 [n + 1 + npoly + 1 + 2 nvert] (mask_start | poly_start | xy, validated here), table_dev: its copy on the HIP device ->
+// int32 [n, C, (C + 31) / 32]: the bit masks of maf_polygon_mask (pixel x of a row in bit x & 31 of word x >> 5).
+Tensor polygon_mask(const Tensor& table, const Tensor& table_dev, int64_t n, int64_t npoly, int64_t nvert, int64_t C) {
+    TORCH_CHECK(n > 0 && npoly >= 0 && nvert >= 0 && C > 0 && n <= MAF_POLYGON_MAX_MASKS && npoly <= MAF_POLYGON_MAX_CONTOURS && nvert <= MAF_POLYGON_MAX_VERTICES && C <= MAF_POLYGON_MAX_CANVAS,
+                "mafyolo::polygon_mask: n, npoly, nvert or C out of range");
+    const int64_t words = n + 1 + npoly + 1 + 2 * nvert;
+    TORCH_CHECK(table.device().is_cpu() && table.scalar_type() == at::kInt && table.is_contiguous() && table.dim() == 1 && table.size(0) == words,
+                "mafyolo::polygon_mask: table is a contiguous CPU int32 [", words, "] array (mask_start | poly_start | xy)");
+    TORCH_CHECK(table_dev.is_cuda() && table_dev.scalar_type() == at::kInt && table_dev.is_contiguous() && table_dev.sizes() == table.sizes(),
+                "mafyolo::polygon_mask: table_dev is the table's contiguous copy on the HIP device (there is no CPU path)");
+    const c10::DeviceGuard device_guard(table_dev.device());
+    Tensor out = at::empty({n, C, (C + 31) / 32}, table_dev.options());
+    check(maf_polygon_mask(table.data_ptr<int32_t>(), table_dev.data_ptr<int32_t>(), (int)n, (int)npoly, (int)nvert, (int)C,
+                           reinterpret_cast<uint32_t*>(out.data_ptr<int32_t>()), stream_of(out)), "polygon_mask");
+    return out;
+}
+
+// mosaic_affine with copy_paste's pixels: paste is the CPU uint8 [B, sizeof(maf_augment_paste_t)] table of mask pointers (validated here),
+// paste_dev its copy on the HIP device.  The caller keeps the masks alive until the current stream has passed this op.
+Tensor mosaic_affine_paste(const Tensor& samples, const Tensor& samples_dev, const Tensor& paste, const Tensor& paste_dev, int64_t S) {
+    const int64_t sz = (int64_t)sizeof(maf_augment_sample_t), pz = (int64_t)sizeof(maf_augment_paste_t);
+    TORCH_CHECK(samples.device().is_cpu() && samples.scalar_type() == at::kByte && samples.is_contiguous() && samples.dim() == 2 && samples.size(1) == sz,
+                "mafyolo::mosaic_affine_paste: samples is a contiguous CPU uint8 [B, ", sz, "] table");
+    TORCH_CHECK(samples_dev.is_cuda() && samples_dev.scalar_type() == at::kByte && samples_dev.is_contiguous() && samples_dev.sizes() == samples.sizes(),
+                "mafyolo::mosaic_affine_paste: samples_dev is the table's contiguous copy on the HIP device (there is no CPU path)");
+    const int64_t B = samples.size(0);
+    TORCH_CHECK(paste.device().is_cpu() && paste.scalar_type() == at::kByte && paste.is_contiguous() && paste.dim() == 2 && paste.size(0) == B && paste.size(1) == pz,
+                "mafyolo::mosaic_affine_paste: paste is a contiguous CPU uint8 [B, ", pz, "] table");
+    TORCH_CHECK(paste_dev.is_cuda() && paste_dev.scalar_type() == at::kByte && paste_dev.is_contiguous() && paste_dev.sizes() == paste.sizes() &&
+                paste_dev.device() == samples_dev.device(),
+                "mafyolo::mosaic_affine_paste: paste_dev is the paste table's contiguous copy on the samples' HIP device");
+    const c10::DeviceGuard device_guard(samples_dev.device());
+    Tensor out = at::empty({B, 3, S, S}, samples_dev.options());
+    check(maf_mosaic_affine_paste(reinterpret_cast<const maf_augment_sample_t*>(samples.data_ptr()), reinterpret_cast<const maf_augment_sample_t*>(samples_dev.data_ptr()),
+                                  reinterpret_cast<const maf_augment_paste_t*>(paste.data_ptr()), reinterpret_cast<const maf_augment_paste_t*>(paste_dev.data_ptr()),
+                                  (int)B, (int)S, out.data_ptr<uint8_t>(), stream_of(out)), "mosaic_affine_paste");
+    return out;
+}
+
 // One batch of the in-process mAP statistics (maf_pr_match): rows / count are the maf_nms result, targets fp32 [N, 6], img_params fp32 [B, 6]
 // (maf_coco_rows' parameters; ignored with MAF_PR_LABELS_XYXY), iouv fp32 [niou].  offs int64: offs[batch] is read, offs[batch + 1] written;
 // keys int64 / masks int16 [capacity] and state int32 [maf_pr_state_ints(nc)] are updated in place (maf-yolo_amd/metrics.py owns them).
@@ -550,6 +591,8 @@ TORCH_LIBRARY(mafyolo, m) {
     m.def("decode_nms(Tensor pred, float conf_thres, float iou_thres, bool agnostic, bool multi_label, int max_det, int[]? classes) -> (Tensor, Tensor)");
     m.def("letterbox(Tensor[] frames, int H, int W, int[] geometry, int[] color, bool bgr) -> Tensor");
     m.def("mosaic_affine(Tensor samples, Tensor samples_dev, int S) -> Tensor");
+    m.def("polygon_mask(Tensor table, Tensor table_dev, int n, int npoly, int nvert, int C) -> Tensor");
+    m.def("mosaic_affine_paste(Tensor samples, Tensor samples_dev, Tensor paste, Tensor paste_dev, int S) -> Tensor");
     m.def("pr_match(Tensor rows, Tensor count, Tensor targets, Tensor img_params, int H, int W, Tensor iouv, int nc, int flags, float cm_conf, "
           "float cm_iou, Tensor(a!) offs, int batch, Tensor(b!) keys, Tensor(c!) masks, Tensor(d!) state) -> ()");
     m.def("pr_curves(Tensor keys, Tensor masks, Tensor state, int nc, int niou) -> Tensor");
@@ -577,6 +620,8 @@ TORCH_LIBRARY_IMPL(mafyolo, CUDA, m) {       // the HIP device is the "CUDA" dis
     m.impl("decode_nms", &decode_nms);
     m.impl("letterbox", &letterbox);
     m.impl("mosaic_affine", &mosaic_affine);
+    m.impl("polygon_mask", &polygon_mask);
+    m.impl("mosaic_affine_paste", &mosaic_affine_paste);
     m.impl("pr_match", &pr_match);
     m.impl("pr_curves", &pr_curves);
     m.impl("coco_append", &coco_append);

@@ -78,6 +78,12 @@ class MafAugmentSample(C.Structure):
                 ("fliplr", C.c_int32), ("reserved", C.c_int32), ("tile", (MafAugmentTile * AUGMENT_MAX_TILES) * 2), ("lut", (C.c_uint8 * 256) * 3)]
 
 
+class MafAugmentPaste(C.Structure):
+    """maf_augment_paste_t: the copy_paste masks of one sample of maf_mosaic_affine_paste (NULL: nothing pasted in that layer) and the canvas side."""
+    _fields_ = [("mask", C.c_void_p * 2), ("C", C.c_int32), ("reserved", C.c_int32)]
+
+
+POLYGON_COORD_MAX = 32767     # MAF_POLYGON_COORD_MAX: |vertex coordinate| maf_polygon_mask accepts
 PR_MAX_DET = 1024             # MAF_PR_MAX_DET / MAF_PR_MAX_LABELS / MAF_PR_MAX_CLASSES: bounds of maf_pr_match / maf_pr_curves
 PR_MAX_LABELS = 1024
 PR_MAX_CLASSES = 1024
@@ -139,7 +145,7 @@ EXPORTS = ["maf_last_error", "maf_version", "maf_op_size", "maf_op_launch", "maf
            "maf_engine_run", "maf_engine_run_filtered", "maf_engine_run_graph", "maf_engine_run_timed", "maf_engine_destroy", "maf_nms_workspace_bytes", "maf_nms", "maf_nms_ex", "maf_nms_debug", "maf_pack_w1x1_bytes", "maf_pack_w1x1", "maf_pack_dw", "maf_pack_batch", "maf_pack_desc_size", "maf_ema_update", "maf_ema_desc_size", "maf_sgd_update", "maf_sgd_desc_size", "maf_nonfinite_check", "maf_range_desc_size", "maf_maxpool_forward", "maf_maxpool_backward", "maf_upsample2x_forward", "maf_upsample2x_backward", "maf_zero", "maf_grad_fold", "maf_add_sub2", "maf_colsum", "maf_dw_wgrad", "maf_dw_wgrad31", "maf_stem_train", "maf_image_to_nhwc8", "maf_bottleneck_record_bytes", "maf_bottleneck_tail_record_bytes", "maf_bottleneck_tail_supported", "maf_conv1dw_record_bytes", "maf_head_tail_record_bytes", "maf_stem2_record_bytes", "maf_conv3s2_lds_record_bytes", "maf_mprep_lds_record_bytes", "maf_mprep_wreg_record_bytes", "maf_conv3s2_wreg_record_bytes", "maf_conv1x1_stats_supported", "maf_coco_rows", "maf_conv1x1_wgrad", "maf_conv_wgrad", "maf_bn_forward", "maf_bn_backward", "maf_bn_backward_acc", "maf_set_deterministic", "maf_dw_branches", "maf_dw_branches_stats", "maf_bn_forward_ex", "maf_bn_replicas", "maf_bn_stats", "maf_bn_sum_forward", "maf_bn_sum_forward_stats", "maf_bn_sum_backward", "maf_tal_targets", "maf_tal_assign", "maf_atss_assign", "maf_loss_partial_rows", "maf_loss_decode", "maf_loss_terms",
            "maf_detect_join", "maf_detect_join_backward", "maf_nhwc_sum", "maf_stream_fork", "maf_stream_join", "maf_tape_fn_id", "maf_tape_fn_nargs", "maf_tape_rec_size", "maf_tape_run", "maf_tape_toggle",
            "maf_stream_create_masked", "maf_stream_destroy", "maf_letterbox", "maf_letterbox_lds_bytes", "maf_rescale_boxes",
-           "maf_augment_resize", "maf_mosaic_affine", "maf_augment_sample_size", "maf_area_struct_sizes", "maf_resize_area",
+           "maf_augment_resize", "maf_mosaic_affine", "maf_augment_sample_size", "maf_polygon_mask", "maf_mosaic_affine_paste", "maf_augment_paste_size", "maf_area_struct_sizes", "maf_resize_area",
            "maf_pr_state_ints", "maf_pr_out_doubles", "maf_pr_workspace_bytes", "maf_pr_match", "maf_pr_curves",
            "maf_coco_append", "maf_coco_match", "maf_coco_accumulate", "maf_jpeg_struct_sizes", "maf_jpeg_progressive_struct_sizes", "maf_jpeg_decode",
            "maf_timer_create", "maf_timer_start", "maf_timer_stop", "maf_timer_elapsed_ms", "maf_timer_destroy"]
@@ -290,6 +296,11 @@ def load():
     lib.maf_augment_resize.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.maf_mosaic_affine.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.maf_augment_sample_size.restype = C.c_int32
+    lib.maf_polygon_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.maf_mosaic_affine_paste.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.maf_augment_paste_size.restype = C.c_int32
+    if lib.maf_augment_paste_size() != C.sizeof(MafAugmentPaste):
+        raise MafError("libmafyolo_hip.so was built for a maf_augment_paste_t of %d bytes, this binding declares %d: rebuild" % (lib.maf_augment_paste_size(), C.sizeof(MafAugmentPaste)))
     if lib.maf_augment_sample_size() != C.sizeof(MafAugmentSample):
         raise MafError("libmafyolo_hip.so was built for a maf_augment_sample_t of %d bytes, this binding declares %d: rebuild" % (lib.maf_augment_sample_size(), C.sizeof(MafAugmentSample)))
     lib.maf_area_struct_sizes.argtypes = [C.POINTER(C.c_int32)]

@@ -9,6 +9,8 @@
     rows, counts = ops.decode_nms(pred, 0.03, 0.65, False, True, 300, None)     # non_max_suppression (yolov6/utils/nms.py:31-105)
     imgs = ops.letterbox(frames, H, W, geometry, [114] * 3, True)  # letterbox + precess_image (data_augment.py:53-82); maf_yolo_amd.letterbox
     imgs = ops.mosaic_affine(samples, samples_dev, 640)            # the pixels of TrainValDataset.__getitem__ (datasets.py:147-275); maf_yolo_amd.train_batch
+    masks = ops.polygon_mask(table, table_dev, n, npoly, nvert, 1280)           # copy_paste's cv2.drawContours(FILLED) masks (data_augment.py:301)
+    imgs = ops.mosaic_affine_paste(samples, samples_dev, paste, paste_dev, 640) # ... and its pixels (data_augment.py:303-305); TrainAugment(polygons=True)
     ops.pr_match(rows, count, targets, img, H, W, iouv, nc, flags, 0.25, 0.45, offs, i, keys, masks, state)  # evaler.py:195-238; metrics.PrMetric.update
     out = ops.pr_curves(keys, masks, state, nc, niou)               # ap_per_class + the summary (evaler.py:240-268); metrics.PrMetric.compute
     img, cat, box, score = ops.coco_append(packed, total, img_index, cat_lut)        # COCOeval results; cocoeval.CocoEval.update
@@ -34,7 +36,7 @@ from . import lib
 ACT_NONE, ACT_RELU, ACT_SILU, ACT_SIGMOID = lib.ACT_NONE, lib.ACT_RELU, lib.ACT_SILU, lib.ACT_SIGMOID
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libmafyolo_torch.so")
 OPS = ("conv1x1_bias_act", "conv3x3s2_bias_act", "dwconv_bias_act", "conv1x1_dgrad", "conv3x3s2_dgrad", "conv_wgrad", "dwconv_dgrad", "dwconv_wgrad",
-       "head_decode", "decode_nms", "mprep", "sppf", "bn_act", "bn_act_backward", "letterbox", "mosaic_affine",
+       "head_decode", "decode_nms", "mprep", "sppf", "bn_act", "bn_act_backward", "letterbox", "mosaic_affine", "polygon_mask", "mosaic_affine_paste",
        "pr_match", "pr_curves", "coco_append", "coco_match", "coco_accumulate")
 _registered = False
 
@@ -99,6 +101,14 @@ def _register():
 
     @L.register_fake("mafyolo::mosaic_affine")
     def _(samples, samples_dev, S):
+        return samples_dev.new_empty((samples.shape[0], 3, S, S), dtype=torch.uint8)
+
+    @L.register_fake("mafyolo::polygon_mask")
+    def _(table, table_dev, n, npoly, nvert, C):
+        return table_dev.new_empty((n, C, (C + 31) // 32), dtype=torch.int32)
+
+    @L.register_fake("mafyolo::mosaic_affine_paste")
+    def _(samples, samples_dev, paste, paste_dev, S):
         return samples_dev.new_empty((samples.shape[0], 3, S, S), dtype=torch.uint8)
 
     @L.register_fake("mafyolo::pr_match")

@@ -1,6 +1,6 @@
 """Measurements of the training augmentation (csrc/augment.hip) on the GPU; prints ONE JSON line.
 
-    python tools/augment_probe.py [--iters N] [--no-torch]
+    python tools/augment_probe.py [--iters N] [--no-torch] [--polygons]
 
 * bs 32 x 640^2 with the MAF-YOLO-n hyp (and a dy_mixup = 1 variant, mixup on most samples): a pool of decoded frames (1080p, 720p and
   480 x 640; > 256 MiB, so the reads come from HBM, not the Infinity Cache) that the batches' draws rotate through.  Per batch: event time of
@@ -8,7 +8,10 @@
   and read back by the tile windows the warp touches, 1.2 MB of output per image).  Kernel times proper come from a rocprofv3 --kernel-trace
   --stats run of this same script (kernels `augment_resize_kernel` and `mosaic_affine_kernel`);
 * the same warp / mixup / HSV / flip rule composed of torch ops on the GPU (gathers + integer arithmetic on the staged frames), timed as the
-  baseline and compared bit for bit with the kernel.
+  baseline and compared bit for bit with the kernel;
+* --polygons: polygon labels with MAF-YOLO-m's hyp (copy_paste 0.2) instead: per batch the event time of train_batch with the pasted
+  contours (maf_polygon_mask + maf_mosaic_affine_paste), of the SAME draws with the contours removed (maf_mosaic_affine), and of the
+  maf_polygon_mask launch alone; the masks' bytes (C^2 / 8 per pasted layer, written once and read by the taps).
 """
 import argparse
 import json
@@ -117,15 +120,94 @@ def torch_rule(table_samples, staged, aug):
     return torch.stack(outs)
 
 
+def polygon_pool(shapes, seed=0):
+    """Seeded polygon labels for the pool: 3..11 polygons of 6..40 vertices per image and the boxes the label reader derives from them."""
+    rs = np.random.RandomState(seed)
+    labels, segments = [], []
+    for _ in shapes:
+        segs, rows = [], []
+        for _ in range(int(rs.randint(3, 12))):
+            k = int(rs.randint(6, 41))
+            c, rad = rs.uniform(0.15, 0.85, 2), rs.uniform(0.03, 0.25, 2)
+            ang = np.sort(rs.uniform(0, 2 * np.pi, k))
+            xy = np.stack([c[0] + rad[0] * np.cos(ang), c[1] + rad[1] * np.sin(ang)], 1).clip(0, 1).astype(np.float32)
+            segs.append(xy)
+            lo, hi = xy.min(0), xy.max(0)
+            rows.append([float(rs.randint(0, 80)), (lo[0] + hi[0]) / 2, (lo[1] + hi[1]) / 2, hi[0] - lo[0], hi[1] - lo[1]])
+        segments.append(segs)
+        labels.append(np.array(rows, np.float32))
+    return labels, segments
+
+
+def _timed(fn, items):
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in items]
+    for (e0, e1), it in zip(ev, items):
+        e0.record()
+        fn(it)
+        e1.record()
+    torch.cuda.synchronize()
+    return [e0.elapsed_time(e1) for e0, e1 in ev]
+
+
+def polygons_case(args, frames, shapes):
+    """train_batch with copy_paste's contours, the same draws without them, and the mask launch alone."""
+    import copy
+    from maf_yolo_amd import lib
+    labels, segments = polygon_pool(shapes)
+    hyp = dict(HYP_N, copy_paste=0.2, mixup=0.1, dy_mixup=0.4)                 # configs/MAF-YOLO-m.py
+    aug = A.TrainAugment(labels, shapes, hyp, 640, segments=segments, polygons=True)
+    random.seed(0)
+    np.random.seed(0)
+    rs = np.random.RandomState(1)
+    batches = [aug.draw_batch(rs.randint(0, len(frames), args.bs)) for _ in range(args.iters)]
+    plain = copy.deepcopy(batches)
+    for b in plain:
+        for smp in b:
+            for layer in smp.layers:
+                layer.paste = []
+    staged = [A.stage_paste(b) for b in batches]
+    L = lib.load()
+    st = torch.cuda.current_stream(DEV).cuda_stream
+    words = 1280 * 40
+    n_max = max(p[1][0] for p in staged if p is not None)
+    masks = torch.empty((n_max, words), dtype=torch.int32, device=DEV)
+    tables = [(p[0], torch.from_numpy(p[0]).to(DEV), p[1]) for p in staged if p is not None]
+
+    def mask_launch(t):
+        tab, tab_dev, (n, npoly, nvert) = t
+        lib.check(L.maf_polygon_mask(tab.ctypes.data, tab_dev.data_ptr(), n, npoly, nvert, 1280, masks.data_ptr(), st))
+    for b, q in zip(batches[:3], plain[:3]):                                   # warm-up
+        M.train_batch(frames, b, aug)
+        M.train_batch(frames, q, aug)
+    torch.cuda.synchronize()
+    with_ms, without_ms = [], []
+    for _ in range(2):                                                         # alternate the two versions: the host is shared
+        with_ms += _timed(lambda b: M.train_batch(frames, b, aug), batches)
+        without_ms += _timed(lambda b: M.train_batch(frames, b, aug), plain)
+    mask_ms = _timed(mask_launch, tables)
+    same = all(torch.equal(M.train_batch(frames, b, aug)[1], M.train_batch(frames, q, aug)[1]) for b, q in zip(batches[:2], plain[:2]))
+    layers = [p[1][0] if p is not None else 0 for p in staged]
+    return dict(train_batch_polygons_ms_median=round(statistics.median(with_ms), 4), train_batch_same_draws_no_paste_ms_median=round(statistics.median(without_ms), 4),
+                polygon_mask_ms_median=round(statistics.median(mask_ms), 4), pasted_layers_per_batch=round(float(np.mean(layers)), 2),
+                contours_per_batch=round(float(np.mean([p[1][1] if p is not None else 0 for p in staged])), 1),
+                vertices_per_batch=round(float(np.mean([p[1][2] if p is not None else 0 for p in staged])), 1),
+                mask_MB_per_batch=round(float(np.mean(layers)) * 1280 * 1280 / 8 / 1e6, 2), targets_equal=bool(same))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=40)
     ap.add_argument("--bs", type=int, default=32)
     ap.add_argument("--no-torch", action="store_true", help="leave the torch-ops baseline out (counter runs: only the kernels' dispatches)")
+    ap.add_argument("--polygons", action="store_true", help="polygon labels: train_batch with and without copy_paste's contours on the same draws")
     args = ap.parse_args()
     frames, shapes, labels = pool(90)                          # 30 x (6.2 + 2.8 + 0.9) MB = 297 MB (283 MiB) of frames
     in_bytes = sum(f.numel() for f in frames)
     out = dict(bs=args.bs, img_size=640, pool_frames=len(frames), pool_MiB=round(in_bytes / 2 ** 20, 1), cases={})
+    if args.polygons:
+        out["cases"]["polygons_maf_yolo_m"] = polygons_case(args, frames, shapes)
+        print(json.dumps(out))
+        return
     for name, hyp in (("maf_yolo_n", HYP_N), ("dy_mixup_1", dict(HYP_N, dy_mixup=1.0, dy_label=100))):
         aug = A.TrainAugment(labels, shapes, hyp, 640)
         random.seed(0)
