@@ -964,6 +964,63 @@ int maf_jpeg_progressive_struct_sizes(int32_t* scan);    /* sizeof(maf_jpeg_scan
 int maf_jpeg_decode(const void* blob_host, const void* blob_dev, int16_t* coef, uint8_t* planes, uint8_t* out, int32_t* status,
                     int32_t stages, maf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------------------
+ * Baseline JPEG encoding on the device (csrc/jpeg_encode.hip): uint8 BGR frames, or rectangles of them, in; the files libjpeg writes with
+ * its defaults out (jpeg_set_quality with force_baseline, JDCT_ISLOW, 4:2:0 or 4:4:4, the standard Huffman tables, JFIF header), bit for bit;
+ * the rules are those of tests/jpeg_encode_ref.py.  The host (maf-yolo_amd/jpeg_encode.py) hands over ONE byte blob, copied to the device as
+ * it is: maf_jpeg_enc_header_t | maf_jpeg_enc_job_t [n_files] | Huffman code tables: uint32 [4][256] (DC luma, DC chroma, AC luma, AC
+ * chroma; length << 16 | code for a symbol, 0 where it has none) | divisors: uint16 [2][64] (luma, chroma; natural order, the quantisation
+ * value, not yet times 8) | the files' headers (everything in front of the scan), byte after byte.
+ *
+ * One chain of launches on `stream` for the whole batch, whatever the number of files; nothing synchronises:
+ *   transform  one thread per 8 x 8 block of the batch, blocks in the order they are coded (MCUs in raster order; Y blocks, Cb, Cr): colour
+ *              conversion straight from the strided frame (jccolor.c), edge padding by index clamping, h2v2 downsampling (jcsample.c), the
+ *              islow FDCT (jfdctint.c), quantisation (jcdctmgr.c) -> int16 [64] per block in zigzag order.
+ *   count      bits per block (jchuff.c) with the DC difference against the nearest coded real block of the same component; a dummy block
+ *              (jccoefct.c) receives that block's DC and costs the fixed DC-category-0 + EOB; sums per 256 blocks.
+ *   offsets    exclusive scan of the bit counts over all blocks of the batch (two levels; 64-bit) -> bitoff [n_blocks + 1].
+ *   pack       every block writes its codes at its bit offset inside its file's region of `packed` (zeroed on the stream by this call;
+ *              words two blocks share are combined with atomicOr); the last block fills the final byte with 1-bits.
+ *   stuff      0xFF bytes counted per MAF_JPEG_ENC_CHUNK packed bytes, scanned per file, file lengths scanned over the batch; then header,
+ *              stuffed scan and EOI of every file are written back to back into `out`: file i at offsets[i], lengths[i] bytes long.
+ * Worst case per block, by which the host sizes `packed` and `out`: MAF_JPEG_ENC_BLOCK_BITS = 22 (the longest DC code, 11 bits for
+ * category 11 of the chroma table, + 11 value bits) + 63 x 26 (a 16-bit AC code + 10 value bits for every coefficient) = 1 660 bits, 208
+ * bytes; twice that once stuffed.  The kernels hold every block to it (sizes are clamped to 11 and 10) whatever the pixels are.
+ * maf_jpeg_encode validates the whole HOST copy of the blob before it touches the device.  It cannot see the frames' allocations: that
+ * `src` + rows x pitch lies inside one is the caller's to check.
+ */
+#define MAF_JPEG_ENC_BLOCK_BITS 1660
+#define MAF_JPEG_ENC_BLOCK_BYTES 208   /* ceil(MAF_JPEG_ENC_BLOCK_BITS / 8) */
+#define MAF_JPEG_ENC_CHUNK 4096        /* bytes of `packed` one workgroup of the stuffing kernels covers; a file's region is whole chunks */
+#define MAF_JPEG_ENC_MAX_BLOCKS (1 << 20)   /* blocks per file: keeps a file's bit offsets inside 31 bits */
+typedef struct {
+    int32_t n_files;
+    int32_t n_blocks;                        /* of the whole batch */
+    int32_t n_chunks;                        /* of the whole batch: `packed` holds n_chunks * MAF_JPEG_ENC_CHUNK bytes */
+    int32_t reserved;
+    int64_t jobs_off, huff_off, quant_off, heads_off;   /* byte offsets of the sections in the blob (16-byte aligned) */
+    int64_t heads_bytes;
+    int64_t total_bytes;                     /* of the blob */
+    int64_t out_bytes;                       /* capacity of `out`: at least the sum over the files of head_len + 2 + 2 * MAF_JPEG_ENC_BLOCK_BYTES * n_blocks */
+} maf_jpeg_enc_header_t;
+typedef struct {
+    const void* src;                         /* device pointer to the first pixel of the frame or rectangle: uint8, pixel stride 3 (B, G, R) */
+    int64_t pitch;                           /* bytes between rows, at least 3 * w */
+    int32_t w, h;                            /* 1 to 65535 */
+    int32_t hs;                              /* luma sampling factor in both directions: 2 (4:2:0) or 1 (4:4:4) */
+    int32_t mcux, mcuy;                      /* ceil(w / (8 hs)), ceil(h / (8 hs)) */
+    int32_t block0, n_blocks;                /* the file's blocks in the batch: n_blocks = mcux * mcuy * (hs * hs + 2) */
+    int32_t chunk0, n_chunks;                /* its region of `packed`: n_chunks = ceil(n_blocks * MAF_JPEG_ENC_BLOCK_BYTES / MAF_JPEG_ENC_CHUNK) */
+    int32_t head_off, head_len;              /* its header inside the heads section */
+    int32_t reserved;
+} maf_jpeg_enc_job_t;
+int maf_jpeg_encode_struct_sizes(int32_t* header_job);   /* sizeof of the two structs above (binding check) */
+/* coef int16 [64 * n_blocks], bits int32 [n_blocks], bitoff int64 [n_blocks + 1], sums int64 [2 * ceil(n_blocks / 256)], packed uint8
+ * [n_chunks * MAF_JPEG_ENC_CHUNK], ffcount int32 [n_chunks], out uint8 [out_bytes], lengths int32 [n_files], offsets int64 [n_files]; all
+ * device buffers, blob_dev / coef / packed 16-byte aligned. */
+int maf_jpeg_encode(const void* blob_host, const void* blob_dev, int16_t* coef, int32_t* bits, int64_t* bitoff, int64_t* sums, uint8_t* packed,
+                    int32_t* ffcount, uint8_t* out, int32_t* lengths, int64_t* offsets, maf_stream_t stream);
+
 /* Diagnostics: shader-clock cycle stamps of image 0 of the last maf_nms call (synchronises the device):
  * [0] sort, [1] kept-list screening, [2] wave resolution, [3] total, [4] candidates, [5] survivors. */
 int maf_nms_debug(uint64_t* host8);
