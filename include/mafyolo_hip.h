@@ -1021,6 +1021,67 @@ int maf_jpeg_encode_struct_sizes(int32_t* header_job);   /* sizeof of the two st
 int maf_jpeg_encode(const void* blob_host, const void* blob_dev, int16_t* coef, int32_t* bits, int64_t* bitoff, int64_t* sums, uint8_t* packed,
                     int32_t* ffcount, uint8_t* out, int32_t* lengths, int64_t* offsets, maf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------------------
+ * PNG decoding on the device (csrc/png_decode.hip): what cv2.imread (IMREAD_COLOR: libpng with png_set_strip_16, png_set_strip_alpha,
+ * png_set_palette_to_rgb, png_set_expand_gray_1_2_4_to_8, png_set_gray_to_rgb, png_set_bgr) returns for a non-interlaced file, bit for
+ * bit; the rules are those of tests/png_ref.py.  The host walks the chunks (maf-yolo_amd/png.py: CRC-32 of the critical chunks, IHDR,
+ * PLTE, the zlib header) and hands over ONE byte blob, copied to the device as it is: maf_png_header_t | maf_png_image_t [n_images] |
+ * palette entries uint8 [n_palette][4] (B, G, R, 0) | the zlib streams of every image (its IDAT payloads concatenated, chunk framing
+ * removed) followed by at least MAF_PNG_STREAM_PAD zero bytes.
+ *
+ * Stages of a call (one chain of launches on `stream`, nothing synchronises; `stages` selects them, MAF_PNG_STAGE_ALL for a decode):
+ *   INFLATE   RFC 1951, one one-wave workgroup per image, every lane decoding the same symbol (no divergence) and the 64 lanes moving the
+ *             bytes of a literal run, a stored block or a match together -> the filtered scanlines, exactly h * (1 + rowbytes) bytes at
+ *             inflated + inf_off.  The Adler-32 is not verified.
+ *   UNFILTER  PNG filter types 0 to 4 undone, lane k of a wave on row y0 + k one pixel behind lane k - 1 -> uint8 [h][rowbytes] at rows +
+ *             rows_off.
+ *   CONVERT   the conversion table of maf-yolo_amd/png.py -> uint8 [h][w][3] BGR at out + out_off.
+ * Bounded by construction: every input byte index is clamped into the stream section and compared with the image's stream_end, past which
+ * the reader feeds zeros; every output index is compared with inflated_size; every distance with the bytes produced so far; every loop has
+ * a bound the host validated or a constant one.  A malformed stream ends with bits of status[image] (MAF_PNG_ST_*) and a zero-filled
+ * remainder.  maf_png_decode validates the whole HOST copy of the blob (every offset, size, count and index) before it touches the device.
+ */
+#define MAF_PNG_STREAM_PAD 64
+#define MAF_PNG_ST_INPUT_EXHAUSTED 1    /* bits past the end of the image's stream were consumed */
+#define MAF_PNG_ST_BAD_BLOCK_TYPE 2     /* BTYPE 3 */
+#define MAF_PNG_ST_BAD_STORED_LEN 4     /* a stored block whose LEN is not ~NLEN */
+#define MAF_PNG_ST_BAD_CODE_LENGTHS 8   /* an over-subscribed or incomplete code, more than 286 / 30 symbols, a repeat with nothing to repeat or past the end, no end-of-block code */
+#define MAF_PNG_ST_NO_CODE 16           /* no code matches the bits, or a length symbol above 285 / a distance symbol above 29 */
+#define MAF_PNG_ST_DISTANCE_TOO_FAR 32  /* a distance larger than the bytes produced so far */
+#define MAF_PNG_ST_TOO_MANY_BYTES 64    /* the stream holds more than inflated_size bytes */
+#define MAF_PNG_ST_TOO_FEW_BYTES 128    /* the stream ends before inflated_size bytes */
+#define MAF_PNG_ST_BAD_FILTER 256       /* a filter type above 4 (the row is taken as type 0) */
+#define MAF_PNG_ST_BAD_PALETTE_INDEX 512 /* a palette index past PLTE (the pixel is black) */
+#define MAF_PNG_STAGE_INFLATE 1
+#define MAF_PNG_STAGE_UNFILTER 2
+#define MAF_PNG_STAGE_CONVERT 4
+#define MAF_PNG_STAGE_ALL 7
+typedef struct {
+    int32_t n_images, n_palette;             /* n_palette: palette entries of the whole call */
+    int64_t images_off, palette_off, stream_off;   /* byte offsets of the sections in the blob (16-byte aligned) */
+    int64_t stream_bytes;                    /* the streams' bytes including the zero padding, a multiple of 8 */
+    int64_t total_bytes;                     /* of the blob */
+    int64_t inflated_bytes, rows_bytes, out_bytes;   /* sizes of the three device buffers */
+} maf_png_header_t;
+typedef struct {
+    int64_t stream_begin, stream_end;        /* the image's deflate bytes inside the stream section: the 2-byte zlib header excluded, the Adler-32 included */
+    int64_t inf_off, rows_off, out_off;      /* bytes, multiples of 16 */
+    int32_t w, h;                            /* 1 to 65535 */
+    int32_t depth, ctype;                    /* IHDR: 1 / 2 / 4 / 8 / 16 and 0 gray, 2 RGB, 3 palette, 4 gray + alpha, 6 RGBA */
+    int32_t rowbytes;                        /* ceil(w * channels * depth / 8) */
+    int32_t bpp;                             /* the filters' byte distance: max(1, channels * depth / 8) */
+    int32_t inflated_size;                   /* h * (1 + rowbytes), below 2^31 */
+    int32_t pal, pal_n;                      /* ctype 3: first palette entry and their number (1 to 256) */
+    int32_t reserved;
+} maf_png_image_t;
+int maf_png_struct_sizes(int32_t* header_image);   /* sizeof of the two structs above (binding check) */
+/* inflated uint8 [inflated_bytes], rows uint8 [rows_bytes], out uint8 [out_bytes], status int32 [n_images]: device buffers, the first three
+ * and blob_dev 16-byte aligned.  status is cleared by the INFLATE stage only; UNFILTER and CONVERT OR their bits into what it holds, and each
+ * stage reads what the stage before it wrote.  A mask without MAF_PNG_STAGE_INFLATE is therefore for measuring a stage on buffers that a full
+ * decode has filled (tools/png_probe.py); a decode passes MAF_PNG_STAGE_ALL. */
+int maf_png_decode(const void* blob_host, const void* blob_dev, uint8_t* inflated, uint8_t* rows, uint8_t* out, int32_t* status,
+                   int32_t stages, maf_stream_t stream);
+
 /* Diagnostics: shader-clock cycle stamps of image 0 of the last maf_nms call (synchronises the device):
  * [0] sort, [1] kept-list screening, [2] wave resolution, [3] total, [4] candidates, [5] survivors. */
 int maf_nms_debug(uint64_t* host8);

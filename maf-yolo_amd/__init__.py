@@ -15,6 +15,9 @@ from .cocoeval import CocoGt, CocoEval  # noqa: F401
 from . import jpeg  # noqa: F401
 from .jpeg import JpegUnsupported  # noqa: F401
 from . import jpeg_encode  # noqa: F401
+from . import png  # noqa: F401
+from .png import PngUnsupported  # noqa: F401
+from . import frames  # noqa: F401
 from .checkpoint import load_checkpoint, reference_state_dict  # noqa: F401
 from .loss import ComputeLoss, task_aligned_assign  # noqa: F401
 from .streams import concurrent_streams  # noqa: F401

@@ -1,0 +1,71 @@
+"""File bytes in, frames out, whatever the kind: the router in front of jpeg.py and png.py.
+
+A folder of the reference's loaders (IMG_FORMATS of yolov6/data/datasets.py, LoadData of yolov6/core/inferer.py) mixes JPEG and PNG files;
+decode(files) sniffs each file's signature, hands the JPEG files to jpeg.decode and the PNG files to png.decode (one call each, so each kind
+keeps its one host -> device copy and its one chain of launches) and returns the frames in input order.
+"""
+import os
+
+from . import jpeg, png
+from .lib import MafError
+
+
+def kind(data):
+    """'jpeg' or 'png' by the signature of a file's bytes, else None."""
+    if data[:8] == png.SIGNATURE:
+        return "png"
+    if data[:2] == b"\xff\xd8":
+        return "jpeg"
+    return None
+
+
+def decode(files, device=None, stream=None, check=True, progressive=False, ignore_orientation=False):
+    """Decode a list of JPEG and PNG files (bytes-like objects or paths, in any mix) on the device -> a list of uint8 [h_i, w_i, 3] BGR CUDA
+    tensors in input order, what cv2.imread returns for each file.  `progressive` and `ignore_orientation` go to jpeg.decode.  With
+    check=False -> (frames, status int32 [len(files)] on the device: each file's status word of its own decoder, merged on `stream` behind the
+    decoders' launches) without synchronising."""
+    files = list(files)
+    if not files:
+        raise MafError("frames.decode: no files")
+    datas, groups = [], {"jpeg": [], "png": []}
+    for i, f in enumerate(files):
+        d = png.file_bytes(f)
+        k = kind(d)
+        if k is None:
+            raise MafError("%s: neither a JPEG nor a PNG signature" % ("file %d (%s)" % (i, os.fspath(f)) if isinstance(f, (str, os.PathLike)) else "file %d" % i))
+        datas.append(d)
+        groups[k].append(i)
+    frames, words, order = [None] * len(files), [], []
+    for k, idx in groups.items():
+        if not idx:
+            continue
+        sub = [datas[i] for i in idx]
+        try:
+            if k == "jpeg":
+                got = jpeg.decode(sub, device=device, stream=stream, ignore_orientation=ignore_orientation, check=check, progressive=progressive)
+            else:
+                got = png.decode(sub, device=device, stream=stream, check=check)
+        except MafError as e:
+            # the decoders number the files of their own call: say which input each one is
+            raise type(e)("%s [%s files of this call are inputs %s]" % (e, k, idx)) from None
+        if not check:
+            got, st = got
+            words.append(st)
+            order += idx
+        for i, fr in zip(idx, got):
+            frames[i] = fr
+    if check:
+        return frames
+    # The status words were written on `stream` (default: the current one) by the decoders' launches, so they are merged THERE, behind those
+    # launches: the words of the two calls back to back, then brought into input order by an index that travels in a pinned buffer
+    # (non_blocking: the host does not wait for it either).
+    import torch
+    dev = words[0].device
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    inverse = [0] * len(files)
+    for at, i in enumerate(order):
+        inverse[i] = at
+    with torch.cuda.device(dev), torch.cuda.stream(st):
+        index = torch.tensor(inverse, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        status = torch.cat(words).index_select(0, index)
+    return frames, status

@@ -147,7 +147,7 @@ EXPORTS = ["maf_last_error", "maf_version", "maf_op_size", "maf_op_launch", "maf
            "maf_stream_create_masked", "maf_stream_destroy", "maf_letterbox", "maf_letterbox_lds_bytes", "maf_rescale_boxes",
            "maf_augment_resize", "maf_mosaic_affine", "maf_augment_sample_size", "maf_polygon_mask", "maf_mosaic_affine_paste", "maf_augment_paste_size", "maf_area_struct_sizes", "maf_resize_area",
            "maf_pr_state_ints", "maf_pr_out_doubles", "maf_pr_workspace_bytes", "maf_pr_match", "maf_pr_curves",
-           "maf_coco_append", "maf_coco_match", "maf_coco_accumulate", "maf_jpeg_struct_sizes", "maf_jpeg_progressive_struct_sizes", "maf_jpeg_decode", "maf_jpeg_encode_struct_sizes", "maf_jpeg_encode",
+           "maf_coco_append", "maf_coco_match", "maf_coco_accumulate", "maf_jpeg_struct_sizes", "maf_jpeg_progressive_struct_sizes", "maf_jpeg_decode", "maf_jpeg_encode_struct_sizes", "maf_jpeg_encode", "maf_png_struct_sizes", "maf_png_decode",
            "maf_timer_create", "maf_timer_start", "maf_timer_stop", "maf_timer_elapsed_ms", "maf_timer_destroy"]
 
 _lib = None
@@ -329,6 +329,8 @@ def load():
     lib.maf_jpeg_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.maf_jpeg_encode_struct_sizes.argtypes = [C.POINTER(C.c_int32)]
     lib.maf_jpeg_encode.argtypes = [C.c_void_p] * 12
+    lib.maf_png_struct_sizes.argtypes = [C.POINTER(C.c_int32)]
+    lib.maf_png_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.maf_timer_create.argtypes = [C.POINTER(C.c_void_p)]
     lib.maf_timer_start.argtypes = [C.c_void_p, C.c_void_p]
     lib.maf_timer_stop.argtypes = [C.c_void_p, C.c_void_p]
