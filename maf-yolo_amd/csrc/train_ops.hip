@@ -344,6 +344,14 @@ int launch_dw_wgrad(DwWgArgs& a, int k, hipStream_t s) {
     const int budget = (int)((long long)abudget / ((long long)a.C * k * k));      // every workgroup ends with C*k*k/nCB atomics: keep their total ~1.5 M
     if (per > budget) per = budget > 8 ? budget : 8;
     const dim3 g(per * a.nCB), b(nthr);
+    if (k == 9 && lds > 64 * 1024) {                                     // 8 groups (the 160 x 160 maps) x the 16 x 24 halo tile of k = 9: 72 KB of LDS
+        static bool attr = false;
+        if (!attr) {
+            int rc = maf_check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_wgrad_kernel<T, V, N, 9>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), "hipFuncSetAttribute(dw_wgrad)");
+            if (rc) return rc;
+            attr = true;
+        }
+    }
     switch (k) {
         case 1: hipLaunchKernelGGL((dw_wgrad_kernel<T, V, N, 1>), g, b, lds, s, a); break;      // the 1 x 1 branch of a DilatedReparamBlock (a per-channel scale): dW[c] = sum dy x
         case 3: hipLaunchKernelGGL((dw_wgrad_kernel<T, V, N, 3>), g, b, lds, s, a); break;

@@ -28,6 +28,7 @@
 namespace {
 
 constexpr int kPix = 64;              // pixels per staging step
+constexpr int kTapsDR = 2;            // 16-byte chunks of dY a thread of wgrad_taps_kernel stages per step: kPix * Cout / 8 <= kTapsDR * 256, i.e. Cout <= 64
 
 struct WgArgs2 {
     const half_t* x; const half_t* dy; float* dw;
@@ -178,7 +179,7 @@ __global__ __launch_bounds__(256) void wgrad_taps_kernel(const WgArgs2 a) {
     half_t* Ds = Xs + 9 * kPix * SX;                                     // [kPix][SD]
     const int ntile1 = tci * tco, ntile = 9 * ntile1;                    // virtual tile vt = (tap * tco + ti) * tci + tj, wave = vt % 4
 
-    constexpr int XR = 10, DR = 2;                                       // 16-byte chunks a thread stages per step (9 * 64 * cib / 8 / 256 <= 9 for cib = 32)
+    constexpr int XR = 10, DR = kTapsDR;                                 // 16-byte chunks a thread stages per step (9 * 64 * cib / 8 / 256 <= 9 for cib = 32; dY: 64 * cob / 8 / 256 <= 2 for cob <= 64, the bound wgrad_launch keeps)
     const int xg = cib >> 3, dg = cob >> 3;
     const int nx = 9 * kPix * xg, nd = kPix * dg;
 
@@ -502,7 +503,10 @@ static int wgrad_launch(const half_t* x, int x_stride, const half_t* dy, int dy_
     static const bool no_taps = getenv("MAF_WGRAD_TAP_PER_WG") != nullptr;     // A/B: one tap per workgroup everywhere
     // (measured, n at batch 32: 8 -> 24 on 640^2 422 -> 246 us; 24 -> 48 on 320^2 190 -> 252 us — with two channel tiles the nine gathers
     //  of X outweigh the eight saved passes over dY: first stem conv only)
-    if (ntaps == 9 && tci == 1 && tco_all * 9 <= 64 && !no_taps) {
+    // Cout <= 64 only: wgrad_taps_kernel stages dY with DR = 2 items per thread, 512 16-byte items per step, and a step holds kPix * 2 * tco_all of them.  (The rule
+    // was tco_all * 9 <= 64, what launch_taps<16> has accumulators for: with 5 .. 7 co tiles the rows from 51 on of every dY step were never written to LDS and the
+    // MFMAs read what lay there.)  Wider layers with one input-channel tile take wgrad_tr_kernel below.
+    if (ntaps == 9 && tci == 1 && kPix * 2 * tco_all <= kTapsDR * 256 && !no_taps) {
         const int steps = maf_cdiv(M, kPix);
         int gx = steps < 1024 ? steps : 1024;
         b.chunk = maf_cdiv(steps, gx) * kPix;
