@@ -70,7 +70,7 @@ def with_static(cands, static):
 
 def conv3_dgrad_tiles(cin, M, static):
     """(tile_p, tile_c, 0) of every launch timed for the data gradient of a 3x3 stride-2 conv with `cin` input channels over M input pixels
-    (csrc/conv_mfma_dgrad.hip: 128-pixel tiles, tile_c in {2, 4, 8}), then `static`."""
+    (csrc/conv_mfma_dgrad.hip: tiles of 64 * tile_p pixels, tile_c in {2, 4, 8}; the library has tile_p 1 and 2 and refuses 4), then `static`."""
     cands = []
     for ct in (2, 4, 8):
         nt = -(-cin // (16 * ct))
