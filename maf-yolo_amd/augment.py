@@ -34,7 +34,7 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
-from . import lib
+from . import lib, staging
 from .letterbox import letterbox_geometry
 from .lib import MafError
 
@@ -437,11 +437,6 @@ def _pitch(f):
     return int(f.stride(0)) if f.shape[0] > 1 else 3 * int(f.shape[1])
 
 
-def _upload(arr, dev):
-    """Host array -> device on the current stream, without a host sync (pinned staging)."""
-    return torch.from_numpy(arr).pin_memory().to(dev, non_blocking=True)
-
-
 def train_batch(frames, indices, aug):
     """TrainValDataset.__getitem__ for every index + collate_fn, on the device -> (imgs uint8 [B, 3, s, s] RGB, targets fp32 [N, 6]
     (image position in the batch, cls, x, y, w, h)), both on the frames' device.
@@ -462,7 +457,7 @@ def train_batch(frames, indices, aug):
     host, dev, keep = stage_batch(frames, samples, aug)
     paste = stage_paste(samples)
     if paste is None:
-        imgs = torch_ops.load().mosaic_affine(host, _upload(host.numpy(), dev), aug.img_size)
+        imgs = torch_ops.load().mosaic_affine(host, staging.upload(host.numpy(), dev), aug.img_size)
     else:
         imgs = _mosaic_affine_paste(host, paste, dev, aug.img_size)
     del keep                                                   # staging and resize tables: stream-ordered frees, after the launch
@@ -474,7 +469,7 @@ def train_batch(frames, indices, aug):
         targets[row:row + k, 0] = b
         targets[row:row + k, 1:] = smp.labels
         row += k
-    return imgs, _upload(targets, dev)
+    return imgs, staging.upload(targets, dev)
 
 
 def stage_paste(samples):
@@ -512,7 +507,7 @@ def _mosaic_affine_paste(host, paste, dev, s):
     buf = np.zeros(int(offs[-1]), np.uint8)
     for o, p in zip(offs, parts):
         buf[o:o + len(p)] = p
-    up = _upload(buf, dev)
+    up = staging.upload(buf, dev)
     samples_dev, paste_dev, table_dev = (up[o:o + len(p)] for o, p in zip(offs, parts))
     st = torch.cuda.current_stream(dev).cuda_stream
     with torch.cuda.device(dev):                               # the C-ABI launches on the current device: the frames' one
@@ -572,7 +567,7 @@ def stage_batch(frames, samples, aug):
             e.dst = where(key)[0]
             e.new_h, e.new_w = src[key][3], src[key][4]
         host = np.frombuffer(tab, np.uint8).copy()
-        tab_dev = _upload(host, dev)
+        tab_dev = staging.upload(host, dev)
         tabs.append(tab_dev)
         lib.check(L.maf_augment_resize(C.addressof(tab), tab_dev.data_ptr(), len(items), st))
     table = (lib.MafAugmentSample * len(samples))()

@@ -1,7 +1,8 @@
-// The pieces the two JPEG entropy kernels share (jpeg_decode.hip: baseline, jpeg_progressive.hip: progressive): the Huffman table layout of
-// include/mafyolo_hip.h, the zigzag order, the clamped 64-bit window bit reader and the symbol decoder of jdhuff.c.
+// The pieces the JPEG files share (jpeg_decode.hip: baseline, jpeg_progressive.hip: progressive, jpeg_encode.hip): the Huffman table layout of
+// include/mafyolo_hip.h, the zigzag order, the constants of the islow DCTs, the clamped 64-bit window bit reader and the symbol decoder of jdhuff.c.
 #pragma once
 #include "maf_common.h"
+#include "image_blob.h"
 
 namespace {
 
@@ -11,9 +12,19 @@ constexpr int LOOK_BITS = 9;
 constexpr int OFF_MAXCODE = 2 << LOOK_BITS, OFF_VALOFF = OFF_MAXCODE + 72, OFF_HUFFVAL = OFF_VALOFF + 72;
 static_assert(OFF_HUFFVAL + 256 == TAB_BYTES, "Huffman table layout");
 
-// jutils.c jpeg_natural_order
-__constant__ uint8_t k_zigzag[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
-                                     35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+// jutils.c jpeg_natural_order, once, in the two forms the kernels read it: k_zigzag in constant memory (the decoders copy it to LDS and
+// index it with decoded values) and ZZ as compile-time indices into a register array (the encoder)
+#define MAF_JPEG_NATURAL_ORDER                                                                                                      \
+    {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,           \
+     35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63}
+__constant__ uint8_t k_zigzag[64] = MAF_JPEG_NATURAL_ORDER;
+constexpr int ZZ[64] = MAF_JPEG_NATURAL_ORDER;
+
+// jidctint.c / jfdctint.c: the fixed-point constants of jpeg_idct_islow and jpeg_fdct_islow
+constexpr int CONST_BITS = 13, PASS1_BITS = 2;
+constexpr int FIX_0_298631336 = 2446, FIX_0_390180644 = 3196, FIX_0_541196100 = 4433, FIX_0_765366865 = 6270, FIX_0_899976223 = 7373,
+              FIX_1_175875602 = 9633, FIX_1_501321110 = 12299, FIX_1_847759065 = 15137, FIX_1_961570560 = 16069, FIX_2_053119869 = 16819,
+              FIX_2_562915447 = 20995, FIX_3_072711026 = 25172;
 
 struct BitReader {
     const uint8_t* buf;       // the scan buffer
@@ -85,9 +96,6 @@ __device__ __forceinline__ int huff_decode(BitReader& br, const uint8_t* tab) {
 
 // HUFF_EXTEND of jdhuff.c
 __device__ __forceinline__ int huff_extend(int r, int s) { return r < (1 << (s - 1)) ? r - (1 << s) + 1 : r; }
-
-// a section of `bytes` at byte offset `off` (16-byte aligned) inside a blob of `total` bytes
-inline bool in_blob(int64_t off, int64_t bytes, int64_t total) { return off >= 0 && (off & 15) == 0 && bytes >= 0 && off <= total && bytes <= total - off; }
 
 }  // namespace
 

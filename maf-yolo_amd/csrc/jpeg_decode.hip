@@ -85,11 +85,7 @@ __global__ __launch_bounds__(MAF_JPEG_GROUP) void jpeg_entropy_kernel(const maf_
     if (fault) atomicOr(&status[lane.image], fault);
 }
 
-// ---- jidctint.c jpeg_idct_islow
-constexpr int CONST_BITS = 13, PASS1_BITS = 2;
-constexpr int FIX_0_298631336 = 2446, FIX_0_390180644 = 3196, FIX_0_541196100 = 4433, FIX_0_765366865 = 6270, FIX_0_899976223 = 7373,
-              FIX_1_175875602 = 9633, FIX_1_501321110 = 12299, FIX_1_847759065 = 15137, FIX_1_961570560 = 16069, FIX_2_053119869 = 16819,
-              FIX_2_562915447 = 20995, FIX_3_072711026 = 25172;
+// ---- jidctint.c jpeg_idct_islow (constants: jpeg_bits.h)
 
 template <int SHIFT>
 __device__ __forceinline__ void idct_1d(const int d[8], int o[8]) {
@@ -185,8 +181,6 @@ __device__ __forceinline__ int chroma_at(const uint8_t* p, int pitch, int x, int
     return (3 * cs + csn + (odd ? 7 : 8)) >> 4;
 }
 
-__device__ __forceinline__ uint32_t clamp255(int v) { return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
-
 __global__ __launch_bounds__(256) void jpeg_color_kernel(const maf_jpeg_image_t* images, const uint8_t* planes, uint8_t* out) {
     const maf_jpeg_image_t im = images[blockIdx.y];
     const int w = im.w, h = im.h;
@@ -211,9 +205,9 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const maf_jpeg_image_t*
             const int cb = chroma_at(pcb, pitch1, x, y, im.hs, im.vs, dw, dh) - 128;
             const int cr = chroma_at(pcr, pitch1, x, y, im.hs, im.vs, dw, dh) - 128;
             // jdcolor.c build_ycc_rgb_table: Cb_b_tab, Cb_g_tab + Cr_g_tab (ONE_HALF folded into the Cb term), Cr_r_tab
-            px[3 * j] = (uint8_t)clamp255(yv + ((116130 * cb + 32768) >> 16));
-            px[3 * j + 1] = (uint8_t)clamp255(yv + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
-            px[3 * j + 2] = (uint8_t)clamp255(yv + ((91881 * cr + 32768) >> 16));
+            px[3 * j] = clamp_u8(yv + ((116130 * cb + 32768) >> 16));
+            px[3 * j + 1] = clamp_u8(yv + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
+            px[3 * j + 2] = clamp_u8(yv + ((91881 * cr + 32768) >> 16));
         }
     }
     const int64_t o = im.out_off + 3 * ((int64_t)y * w + x0);
@@ -237,16 +231,15 @@ extern "C" int maf_jpeg_decode(const void* blob_host, const void* blob_dev, int1
                                int32_t stages, maf_stream_t stream) {
     MAF_REQUIRE(blob_host && blob_dev && coef && planes && out && status, "jpeg_decode: null pointer");
     MAF_REQUIRE(stages > 0 && (stages & ~MAF_JPEG_STAGE_ALL) == 0, "jpeg_decode: stages is a mask of MAF_JPEG_STAGE_*");
-    MAF_REQUIRE((reinterpret_cast<uintptr_t>(blob_dev) & 15) == 0 && (reinterpret_cast<uintptr_t>(coef) & 15) == 0 &&
-                (reinterpret_cast<uintptr_t>(planes) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0, "jpeg_decode: buffers must be 16-byte aligned");
+    MAF_REQUIRE(maf_aligned({blob_dev, coef, planes, out}), "jpeg_decode: buffers must be 16-byte aligned");
     const uint8_t* hb = static_cast<const uint8_t*>(blob_host);
-    const maf_jpeg_header_t hd = *reinterpret_cast<const maf_jpeg_header_t*>(hb);
+    const maf_jpeg_header_t hd = maf_blob_header<maf_jpeg_header_t>(hb);
     const int64_t T = hd.total_bytes;
-    MAF_REQUIRE(hd.n_images > 0 && hd.n_images <= 65535, "jpeg_decode: 1 to 65535 images per call");
+    MAF_REQUIRE(maf_blob_count_ok(hd.n_images), "jpeg_decode: 1 to 65535 images per call");
     const bool prog = hd.n_scans != 0 || hd.n_slanes != 0 || hd.n_rounds != 0;      // progressive files in the call (jpeg_progressive.hip): they have no baseline lanes
     MAF_REQUIRE(hd.group >= 1 && hd.group <= MAF_JPEG_GROUP && (prog ? hd.n_lanes >= 0 : hd.n_lanes > 0) && hd.n_lanes % hd.group == 0 && hd.n_tabsets > 0,
                 "jpeg_decode: the lanes come in whole groups of 1 to MAF_JPEG_GROUP");
-    MAF_REQUIRE(T > 0 && T < ((int64_t)1 << 31), "jpeg_decode: blob size out of range");
+    MAF_REQUIRE(maf_blob_size_ok(T), "jpeg_decode: blob size out of range");
     MAF_REQUIRE(in_blob(hd.images_off, (int64_t)hd.n_images * (int64_t)sizeof(maf_jpeg_image_t), T) &&
                 in_blob(hd.lanes_off, (int64_t)hd.n_lanes * (int64_t)sizeof(maf_jpeg_lane_t), T) &&
                 in_blob(hd.huff_off, (int64_t)hd.n_tabsets * SET_BYTES, T) && in_blob(hd.quant_off, (int64_t)hd.n_images * 3 * 128, T) &&
@@ -297,8 +290,7 @@ extern "C" int maf_jpeg_decode(const void* blob_host, const void* blob_dev, int1
         if (hd.n_lanes > 0) {
             hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(hd.n_lanes / hd.group), dim3(MAF_JPEG_GROUP), 0, s, d_ims,
                                reinterpret_cast<const maf_jpeg_lane_t*>(db + hd.lanes_off), db + hd.huff_off, db + hd.scan_off, hd.scan_bytes, hd.group, coef, status);
-            rc = maf_check_hip(hipGetLastError(), "jpeg_entropy launch");
-            if (rc) return rc;
+            MAF_LAUNCH_CHECK("jpeg_entropy");
         }
         if (prog) {
             rc = maf_jpeg_progressive_launch(hb, db, hd, coef, status, s);
@@ -308,13 +300,11 @@ extern "C" int maf_jpeg_decode(const void* blob_host, const void* blob_dev, int1
     if (stages & MAF_JPEG_STAGE_IDCT) {
         hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + 255) / 256), hd.n_images), dim3(256), 0, s, d_ims,
                            reinterpret_cast<const uint16_t*>(db + hd.quant_off), coef, planes);
-        const int rc = maf_check_hip(hipGetLastError(), "jpeg_idct launch");
-        if (rc) return rc;
+        MAF_LAUNCH_CHECK("jpeg_idct");
     }
     if (stages & MAF_JPEG_STAGE_COLOR) {
         hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)((max_quads + 255) / 256), hd.n_images), dim3(256), 0, s, d_ims, planes, out);
-        const int rc = maf_check_hip(hipGetLastError(), "jpeg_color launch");
-        if (rc) return rc;
+        MAF_LAUNCH_CHECK("jpeg_color");
     }
     return 0;
 }

@@ -35,10 +35,6 @@ constexpr int CHUNK = MAF_JPEG_ENC_CHUNK;
 static_assert(CHUNK == 16 * NT, "a thread of the stuffing kernels owns 16 bytes of a chunk");
 static_assert(MAF_JPEG_ENC_BLOCK_BYTES * 8 >= MAF_JPEG_ENC_BLOCK_BITS && MAF_JPEG_ENC_BLOCK_BITS == 22 + 63 * 26, "worst case of a block");
 
-// jutils.c jpeg_natural_order, as compile-time indices into a register array
-constexpr int ZZ[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
-                        35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
 // the last job whose first block (FIELD = block0) or first chunk (chunk0) is at most i
 template <typename F>
 __device__ __forceinline__ int job_of(int n, int i, F first) {
@@ -78,11 +74,7 @@ __device__ __forceinline__ int prev_real(const maf_jpeg_enc_job_t& j, int m, int
     return (m - 1) * bpm;                                                // block 0 of an MCU is always real
 }
 
-// ---- jfdctint.c jpeg_fdct_islow
-constexpr int CONST_BITS = 13, PASS1_BITS = 2;
-constexpr int FIX_0_298631336 = 2446, FIX_0_390180644 = 3196, FIX_0_541196100 = 4433, FIX_0_765366865 = 6270, FIX_0_899976223 = 7373,
-              FIX_1_175875602 = 9633, FIX_1_501321110 = 12299, FIX_1_847759065 = 15137, FIX_1_961570560 = 16069, FIX_2_053119869 = 16819,
-              FIX_2_562915447 = 20995, FIX_3_072711026 = 25172;
+// ---- jfdctint.c jpeg_fdct_islow (constants: jpeg_bits.h)
 
 template <int N>
 __device__ __forceinline__ int descale(int x) { return (x + (1 << (N - 1))) >> N; }
@@ -415,14 +407,13 @@ extern "C" int maf_jpeg_encode_struct_sizes(int32_t* out) {
 extern "C" int maf_jpeg_encode(const void* blob_host, const void* blob_dev, int16_t* coef, int32_t* bits, int64_t* bitoff, int64_t* sums, uint8_t* packed,
                                int32_t* ffcount, uint8_t* out, int32_t* lengths, int64_t* offsets, maf_stream_t stream) {
     MAF_REQUIRE(blob_host && blob_dev && coef && bits && bitoff && sums && packed && ffcount && out && lengths && offsets, "jpeg_encode: null pointer");
-    MAF_REQUIRE((reinterpret_cast<uintptr_t>(blob_dev) & 15) == 0 && (reinterpret_cast<uintptr_t>(coef) & 15) == 0 && (reinterpret_cast<uintptr_t>(packed) & 15) == 0 &&
-                (reinterpret_cast<uintptr_t>(bitoff) & 7) == 0 && (reinterpret_cast<uintptr_t>(sums) & 7) == 0 && (reinterpret_cast<uintptr_t>(offsets) & 7) == 0,
+    MAF_REQUIRE(maf_aligned({blob_dev, coef, packed}) && maf_aligned({bitoff, sums, offsets}, 8),
                 "jpeg_encode: blob, coef and packed must be 16-byte aligned, the 64-bit buffers 8-byte aligned");
     const uint8_t* hb = static_cast<const uint8_t*>(blob_host);
-    const maf_jpeg_enc_header_t hd = *reinterpret_cast<const maf_jpeg_enc_header_t*>(hb);
+    const maf_jpeg_enc_header_t hd = maf_blob_header<maf_jpeg_enc_header_t>(hb);
     const int64_t T = hd.total_bytes;
-    MAF_REQUIRE(hd.n_files > 0 && hd.n_files <= 65535, "jpeg_encode: 1 to 65535 files per call");
-    MAF_REQUIRE(T > 0 && T < ((int64_t)1 << 31), "jpeg_encode: blob size out of range");
+    MAF_REQUIRE(maf_blob_count_ok(hd.n_files), "jpeg_encode: 1 to 65535 files per call");
+    MAF_REQUIRE(maf_blob_size_ok(T), "jpeg_encode: blob size out of range");
     MAF_REQUIRE(hd.n_blocks > 0 && hd.n_blocks < (1 << 30) && hd.n_chunks > 0 && hd.n_chunks < (1 << 30), "jpeg_encode: block or chunk count out of range");
     MAF_REQUIRE(in_blob(hd.jobs_off, (int64_t)hd.n_files * (int64_t)sizeof(maf_jpeg_enc_job_t), T) && in_blob(hd.huff_off, 4 * 256 * 4, T) &&
                 in_blob(hd.quant_off, 2 * 64 * 2, T) && in_blob(hd.heads_off, hd.heads_bytes, T), "jpeg_encode: a blob section lies outside the blob");
@@ -462,24 +453,25 @@ extern "C" int maf_jpeg_encode(const void* blob_host, const void* blob_dev, int1
     const maf_jpeg_enc_job_t* d_jobs = reinterpret_cast<const maf_jpeg_enc_job_t*>(db + hd.jobs_off);
     const uint32_t* d_huff = reinterpret_cast<const uint32_t*>(db + hd.huff_off);
     const int n_sums = (hd.n_blocks + NT - 1) / NT;
-    int rc = maf_check_hip(hipMemsetAsync(packed, 0, (size_t)hd.n_chunks * CHUNK, s), "jpeg_encode memset");
+    const int rc = maf_check_hip(hipMemsetAsync(packed, 0, (size_t)hd.n_chunks * CHUNK, s), "jpeg_encode memset");
     if (rc) return rc;
     hipLaunchKernelGGL(jpeg_enc_transform_kernel, dim3(n_sums), dim3(NT), 0, s, d_jobs, hd.n_files, hd.n_blocks, reinterpret_cast<const uint16_t*>(db + hd.quant_off), coef);
-    if ((rc = maf_check_hip(hipGetLastError(), "jpeg_enc_transform launch"))) return rc;
+    MAF_LAUNCH_CHECK("jpeg_enc_transform");
     hipLaunchKernelGGL(jpeg_enc_count_kernel, dim3(n_sums), dim3(NT), 0, s, d_jobs, hd.n_files, hd.n_blocks, d_huff, coef, bits, sums);
-    if ((rc = maf_check_hip(hipGetLastError(), "jpeg_enc_count launch"))) return rc;
+    MAF_LAUNCH_CHECK("jpeg_enc_count");
     hipLaunchKernelGGL(jpeg_enc_sums_kernel, dim3(1), dim3(NT), 0, s, sums, n_sums);
-    if ((rc = maf_check_hip(hipGetLastError(), "jpeg_enc_sums launch"))) return rc;
+    MAF_LAUNCH_CHECK("jpeg_enc_sums");
     hipLaunchKernelGGL(jpeg_enc_offsets_kernel, dim3(n_sums), dim3(NT), 0, s, bits, sums, n_sums, hd.n_blocks, bitoff);
-    if ((rc = maf_check_hip(hipGetLastError(), "jpeg_enc_offsets launch"))) return rc;
+    MAF_LAUNCH_CHECK("jpeg_enc_offsets");
     hipLaunchKernelGGL(jpeg_enc_pack_kernel, dim3(n_sums), dim3(NT), 0, s, d_jobs, hd.n_files, hd.n_blocks, d_huff, coef, bitoff, reinterpret_cast<uint32_t*>(packed));
-    if ((rc = maf_check_hip(hipGetLastError(), "jpeg_enc_pack launch"))) return rc;
+    MAF_LAUNCH_CHECK("jpeg_enc_pack");
     hipLaunchKernelGGL(jpeg_enc_ffcount_kernel, dim3(hd.n_chunks), dim3(NT), 0, s, d_jobs, hd.n_files, bitoff, packed, ffcount);
-    if ((rc = maf_check_hip(hipGetLastError(), "jpeg_enc_ffcount launch"))) return rc;
+    MAF_LAUNCH_CHECK("jpeg_enc_ffcount");
     hipLaunchKernelGGL(jpeg_enc_ffscan_kernel, dim3(hd.n_files), dim3(NT), 0, s, d_jobs, bitoff, ffcount, lengths);
-    if ((rc = maf_check_hip(hipGetLastError(), "jpeg_enc_ffscan launch"))) return rc;
+    MAF_LAUNCH_CHECK("jpeg_enc_ffscan");
     hipLaunchKernelGGL(jpeg_enc_lenscan_kernel, dim3(1), dim3(NT), 0, s, lengths, offsets, hd.n_files);
-    if ((rc = maf_check_hip(hipGetLastError(), "jpeg_enc_lenscan launch"))) return rc;
+    MAF_LAUNCH_CHECK("jpeg_enc_lenscan");
     hipLaunchKernelGGL(jpeg_enc_stuff_kernel, dim3(hd.n_chunks), dim3(NT), 0, s, d_jobs, hd.n_files, bitoff, packed, ffcount, offsets, db + hd.heads_off, out, hd.out_bytes);
-    return maf_check_hip(hipGetLastError(), "jpeg_enc_stuff launch");
+    MAF_LAUNCH_CHECK("jpeg_enc_stuff");
+    return 0;
 }

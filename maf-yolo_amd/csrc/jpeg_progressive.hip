@@ -228,8 +228,7 @@ int maf_jpeg_progressive_launch(const uint8_t* hb, const uint8_t* db, const maf_
                            reinterpret_cast<const maf_jpeg_image_t*>(db + hd.images_off), reinterpret_cast<const maf_jpeg_scan_t*>(db + hd.scans_off),
                            reinterpret_cast<const maf_jpeg_lane_t*>(db + hd.slanes_off) + rounds[r], db + hd.huff_off, db + hd.scan_off, hd.scan_bytes,
                            hd.sgroup, coef, status);
-        const int rc = maf_check_hip(hipGetLastError(), "jpeg_prog_entropy launch");
-        if (rc) return rc;
+        MAF_LAUNCH_CHECK("jpeg_prog_entropy");
     }
     return 0;
 }

@@ -26,6 +26,13 @@ int maf_check_hip(hipError_t e, const char* what);
         }                                               \
     } while (0)
 
+// behind a kernel launch: a launch error of kernel `name` is recorded and returned
+#define MAF_LAUNCH_CHECK(name)                                              \
+    do {                                                                    \
+        const int rc_ = maf_check_hip(hipGetLastError(), name " launch");   \
+        if (rc_) return rc_;                                                \
+    } while (0)
+
 // ---- per-kind launchers (each in its own .hip file) ----
 int maf_launch_conv_mfma(const maf_op_t* op, hipStream_t s);   // CONV1X1, CONV3X3S2
 int maf_launch_stem(const maf_op_t* op, hipStream_t s);
@@ -42,6 +49,8 @@ int maf_launch_conv3s2_wreg(const maf_op_t* op, hipStream_t s);
 int maf_dw_wgrad_mfma(const void* x, int x_stride, const void* dy, int dy_stride, int B, int H, int W, int C, int k, float* dw, int replicas, hipStream_t s);
 
 // ---- device helpers ----
+__device__ __forceinline__ uint8_t clamp_u8(int v) { return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
+
 template <int ACT>
 __device__ __forceinline__ float maf_act(float x) {
     if (ACT == MAF_ACT_RELU) return x > 0.f ? x : 0.f;

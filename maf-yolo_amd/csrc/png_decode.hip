@@ -33,6 +33,7 @@
 //     loop bound or an address without such a clamp.
 // A malformed stream ends with status bits and a zero-filled remainder.
 #include "maf_common.h"
+#include "image_blob.h"
 
 namespace {
 
@@ -459,9 +460,6 @@ __global__ __launch_bounds__(256) void png_convert_kernel(const maf_png_image_t*
     if (bad) atomicOr(&status[blockIdx.y], MAF_PNG_ST_BAD_PALETTE_INDEX);
 }
 
-// a section of `bytes` at byte offset `off` (16-byte aligned) inside a blob of `total` bytes
-inline bool png_in_blob(int64_t off, int64_t bytes, int64_t total) { return off >= 0 && (off & 15) == 0 && bytes >= 0 && off <= total && bytes <= total - off; }
-
 }  // namespace
 
 extern "C" int maf_png_struct_sizes(int32_t* out) {
@@ -474,16 +472,15 @@ extern "C" int maf_png_decode(const void* blob_host, const void* blob_dev, uint8
                               int32_t stages, maf_stream_t stream) {
     MAF_REQUIRE(blob_host && blob_dev && inflated && rows && out && status, "png_decode: null pointer");
     MAF_REQUIRE(stages > 0 && (stages & ~MAF_PNG_STAGE_ALL) == 0, "png_decode: stages is a mask of MAF_PNG_STAGE_*");
-    MAF_REQUIRE((reinterpret_cast<uintptr_t>(blob_dev) & 15) == 0 && (reinterpret_cast<uintptr_t>(inflated) & 15) == 0 &&
-                (reinterpret_cast<uintptr_t>(rows) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0, "png_decode: buffers must be 16-byte aligned");
+    MAF_REQUIRE(maf_aligned({blob_dev, inflated, rows, out}), "png_decode: buffers must be 16-byte aligned");
     const uint8_t* hb = static_cast<const uint8_t*>(blob_host);
-    const maf_png_header_t hd = *reinterpret_cast<const maf_png_header_t*>(hb);
+    const maf_png_header_t hd = maf_blob_header<maf_png_header_t>(hb);
     const int64_t T = hd.total_bytes;
-    MAF_REQUIRE(hd.n_images > 0 && hd.n_images <= 65535, "png_decode: 1 to 65535 images per call");
-    MAF_REQUIRE(T > 0 && T < ((int64_t)1 << 31), "png_decode: blob size out of range");
+    MAF_REQUIRE(maf_blob_count_ok(hd.n_images), "png_decode: 1 to 65535 images per call");
+    MAF_REQUIRE(maf_blob_size_ok(T), "png_decode: blob size out of range");
     MAF_REQUIRE(hd.n_palette >= 0 && hd.n_palette <= 256 * hd.n_images, "png_decode: palette entry count out of range");
-    MAF_REQUIRE(png_in_blob(hd.images_off, (int64_t)hd.n_images * (int64_t)sizeof(maf_png_image_t), T) && png_in_blob(hd.palette_off, (int64_t)hd.n_palette * 4, T) &&
-                png_in_blob(hd.stream_off, hd.stream_bytes, T) && hd.stream_bytes >= MAF_PNG_STREAM_PAD && hd.stream_bytes % 8 == 0,
+    MAF_REQUIRE(in_blob(hd.images_off, (int64_t)hd.n_images * (int64_t)sizeof(maf_png_image_t), T) && in_blob(hd.palette_off, (int64_t)hd.n_palette * 4, T) &&
+                in_blob(hd.stream_off, hd.stream_bytes, T) && hd.stream_bytes >= MAF_PNG_STREAM_PAD && hd.stream_bytes % 8 == 0,
                 "png_decode: a blob section lies outside the blob");
     MAF_REQUIRE(hd.inflated_bytes > 0 && hd.rows_bytes > 0 && hd.out_bytes > 0, "png_decode: empty output buffers");
     const maf_png_image_t* ims = reinterpret_cast<const maf_png_image_t*>(hb + hd.images_off);
@@ -516,22 +513,19 @@ extern "C" int maf_png_decode(const void* blob_host, const void* blob_dev, uint8
     const uint8_t* db = static_cast<const uint8_t*>(blob_dev);
     const maf_png_image_t* d_ims = reinterpret_cast<const maf_png_image_t*>(db + hd.images_off);
     if (stages & MAF_PNG_STAGE_INFLATE) {
-        int rc = maf_check_hip(hipMemsetAsync(status, 0, (size_t)hd.n_images * sizeof(int32_t), s), "png_decode memset");
+        const int rc = maf_check_hip(hipMemsetAsync(status, 0, (size_t)hd.n_images * sizeof(int32_t), s), "png_decode memset");
         if (rc) return rc;
         hipLaunchKernelGGL(png_inflate_kernel, dim3(hd.n_images), dim3(64), 0, s, d_ims, db + hd.stream_off, hd.stream_bytes, inflated, status);
-        rc = maf_check_hip(hipGetLastError(), "png_inflate launch");
-        if (rc) return rc;
+        MAF_LAUNCH_CHECK("png_inflate");
     }
     if (stages & MAF_PNG_STAGE_UNFILTER) {
         hipLaunchKernelGGL(png_unfilter_kernel, dim3(hd.n_images), dim3(64), 0, s, d_ims, inflated, rows, status);
-        const int rc = maf_check_hip(hipGetLastError(), "png_unfilter launch");
-        if (rc) return rc;
+        MAF_LAUNCH_CHECK("png_unfilter");
     }
     if (stages & MAF_PNG_STAGE_CONVERT) {
         hipLaunchKernelGGL(png_convert_kernel, dim3((unsigned)((max_quads + 255) / 256), hd.n_images), dim3(256), 0, s, d_ims,
                            reinterpret_cast<const uint32_t*>(db + hd.palette_off), rows, out, status);
-        const int rc = maf_check_hip(hipGetLastError(), "png_convert launch");
-        if (rc) return rc;
+        MAF_LAUNCH_CHECK("png_convert");
     }
     return 0;
 }

@@ -25,8 +25,6 @@ namespace {
 constexpr int AR_ROWS = 4;                 // output rows per workgroup
 constexpr int THREADS = 256;
 
-__device__ __forceinline__ uint8_t sat_u8(int v) { return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
-
 __global__ __launch_bounds__(THREADS) void resize_area_kernel(const maf_area_frame_t* __restrict__ frames, const int32_t* __restrict__ tab) {
     const maf_area_frame_t f = frames[blockIdx.y];
     const int y0 = blockIdx.x * AR_ROWS;
@@ -52,9 +50,9 @@ __global__ __launch_bounds__(THREADS) void resize_area_kernel(const maf_area_fra
             for (int r = 0; r < ky; ++r, s += f.src_pitch)
                 for (int k = 0; k < kx; ++k) { a0 += s[3 * k]; a1 += s[3 * k + 1]; a2 += s[3 * k + 2]; }
             uint8_t* d = f.dst + ((size_t)y * nw + x) * 3;
-            d[0] = sat_u8(__float2int_rn((float)a0 * inv));
-            d[1] = sat_u8(__float2int_rn((float)a1 * inv));
-            d[2] = sat_u8(__float2int_rn((float)a2 * inv));
+            d[0] = clamp_u8(__float2int_rn((float)a0 * inv));
+            d[1] = clamp_u8(__float2int_rn((float)a1 * inv));
+            d[2] = clamp_u8(__float2int_rn((float)a2 * inv));
         }
     } else {
         const int32_t* xs = tab + f.x_start;
@@ -82,9 +80,9 @@ __global__ __launch_bounds__(THREADS) void resize_area_kernel(const maf_area_fra
                 else { s0 = s0 + beta * b0; s1 = s1 + beta * b1; s2 = s2 + beta * b2; }
             }
             uint8_t* d = f.dst + ((size_t)y * nw + x) * 3;
-            d[0] = sat_u8(__float2int_rn(s0));
-            d[1] = sat_u8(__float2int_rn(s1));
-            d[2] = sat_u8(__float2int_rn(s2));
+            d[0] = clamp_u8(__float2int_rn(s0));
+            d[1] = clamp_u8(__float2int_rn(s1));
+            d[2] = clamp_u8(__float2int_rn(s2));
         }
     }
 }
@@ -152,5 +150,6 @@ extern "C" int maf_resize_area(const maf_area_frame_t* frames, const maf_area_fr
     }
     hipLaunchKernelGGL(resize_area_kernel, dim3((max_h + AR_ROWS - 1) / AR_ROWS, n), dim3(THREADS), 0, static_cast<hipStream_t>(stream), frames_dev,
                        static_cast<const int32_t*>(tables_dev));
-    return maf_check_hip(hipGetLastError(), "resize_area launch");
+    MAF_LAUNCH_CHECK("resize_area");
+    return 0;
 }

@@ -4,9 +4,7 @@ A folder of the reference's loaders (IMG_FORMATS of yolov6/data/datasets.py, Loa
 decode(files) sniffs each file's signature, hands the JPEG files to jpeg.decode and the PNG files to png.decode (one call each, so each kind
 keeps its one host -> device copy and its one chain of launches) and returns the frames in input order.
 """
-import os
-
-from . import jpeg, png
+from . import jpeg, png, staging
 from .lib import MafError
 
 
@@ -29,10 +27,10 @@ def decode(files, device=None, stream=None, check=True, progressive=False, ignor
         raise MafError("frames.decode: no files")
     datas, groups = [], {"jpeg": [], "png": []}
     for i, f in enumerate(files):
-        d = png.file_bytes(f)
+        d = staging.file_bytes(f)
         k = kind(d)
         if k is None:
-            raise MafError("%s: neither a JPEG nor a PNG signature" % ("file %d (%s)" % (i, os.fspath(f)) if isinstance(f, (str, os.PathLike)) else "file %d" % i))
+            raise MafError("%s: neither a JPEG nor a PNG signature" % staging.file_name(f, i))
         datas.append(d)
         groups[k].append(i)
     frames, words, order = [None] * len(files), [], []

@@ -18,14 +18,15 @@ tables and the restart interval in force there); csrc/jpeg_progressive.hip decod
 and colour kernels run unchanged on the finished coefficients (rules restated in tests/jpeg_progressive_ref.py).  A progression that leaves
 a coefficient unfinished (libjpeg would smooth it) or that libjpeg warns about raises JpegUnsupported.  Without the flag nothing changes.
 """
-import os
 import struct
 from collections import namedtuple
+from functools import partial
 
 import numpy as np
 
-from . import lib
+from . import lib, staging
 from .lib import MafError
+from .staging import align as _align, file_bytes as _bytes
 
 
 class JpegUnsupported(MafError):
@@ -55,13 +56,6 @@ _SOF_NAMES = {0xC1: "extended sequential DCT (SOF1)", 0xC2: "progressive DCT (SO
               0xC5: "differential sequential DCT (SOF5)", 0xC6: "differential progressive DCT (SOF6)", 0xC7: "differential lossless (SOF7)",
               0xC9: "arithmetic coding (SOF9)", 0xCA: "arithmetic coding (SOF10, progressive)", 0xCB: "arithmetic coding (SOF11, lossless)",
               0xCD: "arithmetic coding (SOF13)", 0xCE: "arithmetic coding (SOF14)", 0xCF: "arithmetic coding (SOF15)"}
-
-
-def _bytes(data):
-    if isinstance(data, (str, os.PathLike)):
-        with open(data, "rb") as f:
-            return f.read()
-    return bytes(data)
 
 
 def _exif_orientation(seg):
@@ -515,10 +509,6 @@ def _group_of(n_lanes):
     return group
 
 
-def _align(x, a=16):
-    return (x + a - 1) // a * a
-
-
 def build_blob(datas, infos):
     """Everything the device needs for one call, in one byte array: header | image table | lane table | Huffman table sets | quantisation
     tables | with progressive files: scan table | scan lanes | round starts | the scans' bytes + SCAN_PAD zeros.
@@ -591,44 +581,30 @@ def build_blob(datas, infos):
         for ts, g in r.items():
             srows += g + [(0, 0, -1, 0, 0, ts)] * (-len(g) % sgroup)
         starts.append(len(srows))
-    scans, slanes, round_at = np.array(scan_rows, SCAN_DT), np.array(srows, LANE_DT), np.array(starts, np.int32)
-    hdr = np.zeros(1, HEADER_DT)[0]
-    off = _align(HEADER_DT.itemsize)
+    huff = np.concatenate(set_bytes)
+    prog = (np.array(scan_rows, SCAN_DT), np.array(srows, LANE_DT), np.array(starts, np.int32)) if scan_rows else None
+    hdr, off = staging.blob_layout(HEADER_DT, _sections(images, lanes, huff, quant, prog))
     hdr["n_images"], hdr["n_lanes"], hdr["n_tabsets"], hdr["group"] = B, len(lanes), len(set_bytes), group
-    hdr["images_off"] = off
-    off = _align(off + images.nbytes)
-    hdr["lanes_off"] = off
-    off = _align(off + lanes.nbytes)
-    hdr["huff_off"] = off
-    off = _align(off + HUFF_SET_BYTES * len(set_bytes))
-    hdr["quant_off"] = off
-    off = _align(off + quant.nbytes)
-    if scan_rows:                                            # a call without progressive files has none of these sections
-        hdr["n_scans"], hdr["n_slanes"], hdr["n_rounds"], hdr["sgroup"] = len(scans), len(slanes), len(rounds), sgroup
-        hdr["scans_off"] = off
-        off = _align(off + scans.nbytes)
-        hdr["slanes_off"] = off
-        off = _align(off + slanes.nbytes)
-        hdr["rounds_off"] = off
-        off = _align(off + round_at.nbytes)
+    if prog is not None:                                     # a call without progressive files has none of these sections
+        hdr["n_scans"], hdr["n_slanes"], hdr["n_rounds"], hdr["sgroup"] = len(prog[0]), len(prog[1]), len(rounds), sgroup
     hdr["scan_off"] = off
     hdr["scan_bytes"] = _align(scanb + SCAN_PAD)           # a multiple of 8: the bit reader loads aligned 8-byte words
     hdr["total_bytes"] = off + _align(scanb + SCAN_PAD)
     hdr["coef_elems"], hdr["plane_bytes"], hdr["out_bytes"] = coef, plane, outb
-    if hdr["total_bytes"] >= 2 ** 31 or B > 65535:
+    if hdr["total_bytes"] >= staging.MAX_BLOB or B > staging.MAX_FILES:
         raise MafError("jpeg: decode() takes up to 65535 files and 2 GiB of file bytes per call")
-    return hdr, images, lanes, np.concatenate(set_bytes), quant, scan_at, ((scans, slanes, round_at) if scan_rows else None)
+    return hdr, images, lanes, huff, quant, scan_at, prog
+
+
+def _sections(images, lanes, huff, quant, prog):
+    """The sections in front of the scan bytes, by header field, in blob order."""
+    return [("images_off", images), ("lanes_off", lanes), ("huff_off", huff), ("quant_off", quant)] + \
+        (list(zip(("scans_off", "slanes_off", "rounds_off"), prog)) if prog is not None else [])
 
 
 def fill_blob(buf, hdr, images, lanes, huff, quant, datas, infos, scan_at, prog=None):
     """Write the sections of build_blob into `buf` (a uint8 array of hdr.total_bytes: the pinned staging buffer)."""
-    buf[:HEADER_DT.itemsize] = np.frombuffer(hdr.tobytes(), np.uint8)
-    sections = [("images_off", images), ("lanes_off", lanes), ("huff_off", huff), ("quant_off", quant)]
-    if prog is not None:
-        sections += zip(("scans_off", "slanes_off", "rounds_off"), prog)
-    for name, arr in sections:
-        o = int(hdr[name])
-        buf[o:o + arr.nbytes] = arr.reshape(-1).view(np.uint8)
+    staging.write_blob(buf, hdr, _sections(images, lanes, huff, quant, prog))
     so = int(hdr["scan_off"])
     for d, info, at in zip(datas, infos, scan_at):
         s, e = info.scan
@@ -636,32 +612,9 @@ def fill_blob(buf, hdr, images, lanes, huff, quant, datas, infos, scan_at, prog=
     buf[so + (scan_at[-1] + infos[-1].scan[1] - infos[-1].scan[0] if infos else 0):] = 0      # at least SCAN_PAD zero bytes
 
 
-_lib_checked = False
-
-
-def _library():
-    """The HIP library, with the struct sizes of this binding checked against it once."""
-    global _lib_checked
-    L = lib.load()
-    if not _lib_checked:
-        import ctypes
-        sizes = (ctypes.c_int32 * 3)()
-        lib.check(L.maf_jpeg_struct_sizes(sizes))
-        sizes_p = (ctypes.c_int32 * 1)()
-        lib.check(L.maf_jpeg_progressive_struct_sizes(sizes_p))
-        have, want = list(sizes) + list(sizes_p), [HEADER_DT.itemsize, IMAGE_DT.itemsize, LANE_DT.itemsize, SCAN_DT.itemsize]
-        if have != want:
-            raise MafError("libmafyolo_hip.so was built for maf_jpeg_* structs of %s bytes, this binding declares %s: rebuild" % (have, want))
-        _lib_checked = True
-    return L
-
-
-def _name(f, i):
-    return "file %d (%s)" % (i, os.fspath(f)) if isinstance(f, (str, os.PathLike)) else "file %d" % i
-
-
-def status_text(word):
-    return ", ".join(t for bit, t in _STATUS_TEXT if word & bit) or "status 0x%x" % word
+_library = partial(staging.checked_library, "jpeg", (("maf_jpeg_struct_sizes", 3), ("maf_jpeg_progressive_struct_sizes", 1)),
+                   [HEADER_DT.itemsize, IMAGE_DT.itemsize, LANE_DT.itemsize, SCAN_DT.itemsize], "maf_jpeg_* structs")
+status_text = partial(staging.status_text, _STATUS_TEXT)
 
 
 def decode(files, device=None, stream=None, ignore_orientation=False, check=True, stages=STAGE_ALL, taps=None, progressive=False):
@@ -673,51 +626,26 @@ def decode(files, device=None, stream=None, ignore_orientation=False, check=True
     (frames, status int32 [B]) without synchronising.  `stream`: a torch.cuda.Stream to work on (default: the current one).
     `taps`: a dict that receives the intermediate buffers (coefficients, planes, the image table; "progressive": the scan table, the scan
     lanes and the round starts, or None) — tests and the probe."""
-    import torch
-    files = list(files)
-    if not files:
-        raise MafError("jpeg.decode: no files")
-    dev = torch.device("cuda" if device is None else device)
-    if dev.type != "cuda":
-        raise MafError("jpeg.decode runs on the HIP path only (no CPU fallback): device %s" % dev)
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    datas, infos = [], []
-    for i, f in enumerate(files):
-        d = _bytes(f)
-        try:
-            info = parse(d, progressive)
-        except MafError as e:
-            raise type(e)("%s: %s" % (_name(f, i), e)) from None
+    extra = {}
+
+    def parse_one(d):
+        info = parse(d, progressive)
         if info.orientation not in (None, 1) and not ignore_orientation:
-            raise JpegUnsupported("%s: jpeg: EXIF orientation %d — cv2.imread would rotate the frame, this decoder does not "
-                                  "(pass ignore_orientation=True to take the stored pixels)" % (_name(f, i), info.orientation))
-        datas.append(d)
-        infos.append(info)
-    hdr, images, lanes, huff, quant, scan_at, prog = build_blob(datas, infos)
-    L = _library()
-    st = stream if stream is not None else torch.cuda.current_stream(dev)
-    with torch.cuda.device(dev), torch.cuda.stream(st):
-        stage = torch.empty(int(hdr["total_bytes"]), dtype=torch.uint8, pin_memory=True)
-        host = stage.numpy()
-        fill_blob(host, hdr, images, lanes, huff, quant, datas, infos, scan_at, prog)
-        blob = stage.to(dev, non_blocking=True)                                  # the call's one host -> device copy
-        coef = torch.empty(int(hdr["coef_elems"]), dtype=torch.int16, device=dev)
-        planes = torch.empty(int(hdr["plane_bytes"]), dtype=torch.uint8, device=dev)
-        out = torch.empty(int(hdr["out_bytes"]), dtype=torch.uint8, device=dev)
-        status = torch.empty(len(files), dtype=torch.int32, device=dev)
-        lib.check(L.maf_jpeg_decode(host.ctypes.data, blob.data_ptr(), coef.data_ptr(), planes.data_ptr(), out.data_ptr(), status.data_ptr(),
-                                    int(stages), st.cuda_stream))
-        frames = []
-        for im in images:
-            o, h, w = int(im["out_off"]), int(im["h"]), int(im["w"])
-            frames.append(out[o:o + 3 * h * w].view(h, w, 3))
-        if taps is not None:
-            taps.update(coef=coef, planes=planes, images=images, status=status, header=hdr, progressive=prog)
-        if not check:
-            return frames, status
-        words = status.tolist()                                                  # the one synchronisation (it also keeps `stage` alive until the copy is done)
-    bad = [(i, w) for i, w in enumerate(words) if w]
-    if bad:
-        raise MafError("jpeg.decode: " + "; ".join("%s: %s" % (_name(files[i], i), status_text(w)) for i, w in bad))
-    return frames
+            raise JpegUnsupported("jpeg: EXIF orientation %d — cv2.imread would rotate the frame, this decoder does not "
+                                  "(pass ignore_orientation=True to take the stored pixels)" % info.orientation)
+        return info
+
+    def build(datas, infos):
+        hdr, images, lanes, huff, quant, scan_at, prog = build_blob(datas, infos)
+        extra["progressive"] = prog
+        return hdr, images, lambda host: fill_blob(host, hdr, images, lanes, huff, quant, datas, infos, scan_at, prog)
+
+    def launch(L, s, blob, hdr, out, status):
+        import torch
+        coef = torch.empty(int(hdr["coef_elems"]), dtype=torch.int16, device=s.dev)
+        planes = torch.empty(int(hdr["plane_bytes"]), dtype=torch.uint8, device=s.dev)
+        lib.check(L.maf_jpeg_decode(s.host.ctypes.data, blob.data_ptr(), coef.data_ptr(), planes.data_ptr(), out.data_ptr(), status.data_ptr(),
+                                    int(stages), s.stream.cuda_stream))
+        return dict(extra, coef=coef, planes=planes)
+
+    return staging.decode_files("jpeg.decode", files, parse_one, build, _library, launch, _STATUS_TEXT, False, device, stream, check, taps)

@@ -15,11 +15,11 @@ anyone: parity is claimed with libjpeg as Pillow drives it only.  No CPU fallbac
 Not done: grayscale output, 4:2:2, optimised Huffman tables, progressive output, restart intervals, EXIF, drawing boxes or text on frames
 (plot_box_and_label), video.
 """
-import ctypes
+from functools import partial
 
 import numpy as np
 
-from . import lib
+from . import lib, staging
 from .lib import MafError
 
 ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
@@ -163,53 +163,20 @@ class EncodedBatch:
         return self._files
 
 
-_lib_checked = False
+_library = partial(staging.checked_library, "jpeg_encode", (("maf_jpeg_encode_struct_sizes", 2),), [HEADER_DT.itemsize, JOB_DT.itemsize],
+                   "maf_jpeg_enc_* structs")
 
-
-def _library():
-    global _lib_checked
-    L = lib.load()
-    if not _lib_checked:
-        sizes = (ctypes.c_int32 * 2)()
-        lib.check(L.maf_jpeg_encode_struct_sizes(sizes))
-        if list(sizes) != [HEADER_DT.itemsize, JOB_DT.itemsize]:
-            raise MafError("libmafyolo_hip.so was built for maf_jpeg_enc_* structs of %s bytes, this binding declares %s: rebuild"
-                           % (list(sizes), [HEADER_DT.itemsize, JOB_DT.itemsize]))
-        _lib_checked = True
-    return L
-
-
-def _align(x, a=16):
-    return (x + a - 1) // a * a
-
-
-def _frame_list(frames):
-    import torch
-    if isinstance(frames, torch.Tensor):
-        if frames.dim() != 4:
-            raise MafError("jpeg_encode.encode: a tensor of frames is [B, h, w, 3], got %s" % (tuple(frames.shape),))
-        frames = list(frames.unbind(0))
-    frames = list(frames)
-    if not frames:
-        raise MafError("jpeg_encode.encode: no frames")
-    for i, f in enumerate(frames):
-        if not isinstance(f, torch.Tensor):
-            raise MafError("jpeg_encode.encode: frame %d is a %s, not a CUDA tensor" % (i, type(f).__name__))
-        if not f.is_cuda:
-            raise MafError("jpeg_encode.encode runs on the HIP path only (no CPU fallback): frame %d is on %s" % (i, f.device))
-        if f.device != frames[0].device:
-            raise MafError("jpeg_encode.encode: frame %d is on %s, frame 0 on %s" % (i, f.device, frames[0].device))
-        if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3:
-            raise MafError("jpeg_encode.encode: frame %d must be uint8 [h, w, 3] BGR, got %s %s" % (i, f.dtype, tuple(f.shape)))
-        h, w = int(f.shape[0]), int(f.shape[1])
-        if h == 0 or w == 0:
-            raise MafError("jpeg_encode.encode: frame %d is empty (%d x %d): there is no JPEG file of an empty image" % (i, w, h))
-        if h > 65535 or w > 65535:
-            raise MafError("jpeg_encode.encode: frame %d is %d x %d, a JPEG dimension is at most 65535" % (i, w, h))
-        if f.stride(2) != 1 or f.stride(1) != 3 or (h > 1 and f.stride(0) < 3 * w):
-            raise MafError("jpeg_encode.encode: frame %d must have pixel stride 3 and channel stride 1 (any row pitch of at least 3 * w), got strides %s"
-                           % (i, tuple(f.stride())))
-    return frames
+_FRAME_TEXT = {      # staging.frame_list in encode()'s words
+    "batch": "jpeg_encode.encode: a tensor of frames is [B, h, w, 3], got %(shape)s",
+    "none": "jpeg_encode.encode: no frames",
+    "not_tensor": "jpeg_encode.encode: frame %(i)d is a %(kind)s, not a CUDA tensor",
+    "cpu": "jpeg_encode.encode runs on the HIP path only (no CPU fallback): frame %(i)d is on %(device)s",
+    "device": "jpeg_encode.encode: frame %(i)d is on %(device)s, frame 0 on %(first)s",
+    "type": "jpeg_encode.encode: frame %(i)d must be uint8 [h, w, 3] BGR, got %(dtype)s %(shape)s",
+    "empty": "jpeg_encode.encode: frame %(i)d is empty (%(w)d x %(h)d): there is no JPEG file of an empty image",
+    "too_large": "jpeg_encode.encode: frame %(i)d is %(w)d x %(h)d, a JPEG dimension is at most 65535",
+    "stride": "jpeg_encode.encode: frame %(i)d must have pixel stride 3 and channel stride 1 (any row pitch of at least 3 * w), got strides %(strides)s"}
+_FRAME_TEXT["pitch"] = _FRAME_TEXT["stride"]
 
 
 def encode(frames, quality=95, subsampling="4:2:0", rects=None, stream=None, taps=None):
@@ -225,7 +192,7 @@ def encode(frames, quality=95, subsampling="4:2:0", rects=None, stream=None, tap
     if subsampling not in SAMPLING:
         raise MafError("jpeg_encode.encode: subsampling is \"4:2:0\" or \"4:4:4\", got %r (4:2:2 and grayscale are not written)" % (subsampling,))
     quality, hs = int(quality), SAMPLING[subsampling]
-    frames = _frame_list(frames)
+    frames = staging.frame_list(frames, _FRAME_TEXT)
     fh = np.array([f.shape[0] for f in frames], np.int64)
     fw = np.array([f.shape[1] for f in frames], np.int64)
     if rects is None:
@@ -250,7 +217,7 @@ def encode(frames, quality=95, subsampling="4:2:0", rects=None, stream=None, tap
             k = int(bad[0])
             raise MafError("jpeg_encode.encode: rectangle %d (%d, %d, %d, %d) is empty: there is no JPEG file of an empty image" % (k, x1[k], y1[k], x2[k], y2[k]))
     n = len(fi)
-    if n > 65535:
+    if n > staging.MAX_FILES:
         raise MafError("jpeg_encode.encode takes up to 65535 files per call")
     qluma, qchroma = quant_table(QUANT_LUMA, quality), quant_table(QUANT_CHROMA, quality)
     w, h = x2 - x1, y2 - y1
@@ -279,30 +246,20 @@ def encode(frames, quality=95, subsampling="4:2:0", rects=None, stream=None, tap
     codes = np.concatenate([huff_code_table(*t) for t in HUFFMAN])
     quant = np.stack([qluma, qchroma]).astype(np.uint16)
     head_bytes = heads.reshape(-1)
-    hdr = np.zeros(1, HEADER_DT)[0]
-    off = _align(HEADER_DT.itemsize)
+    sections = (("jobs_off", jobs), ("huff_off", codes), ("quant_off", quant), ("heads_off", head_bytes))
+    hdr, off = staging.blob_layout(HEADER_DT, sections)
     hdr["n_files"], hdr["n_blocks"], hdr["n_chunks"] = n, block, chunk
-    sections = []
-    for name, arr in (("jobs_off", jobs), ("huff_off", codes), ("quant_off", quant), ("heads_off", head_bytes)):
-        hdr[name] = off
-        sections.append((off, arr))
-        off = _align(off + arr.nbytes)
     hdr["heads_bytes"], hdr["total_bytes"], hdr["out_bytes"] = head_bytes.nbytes, off, out_bytes
-    if off >= 2 ** 31:
+    if off >= staging.MAX_BLOB:
         raise MafError("jpeg_encode.encode: the job table of one call is limited to 2 GiB")
     L = _library()
     dev = frames[0].device
-    st = stream if stream is not None else torch.cuda.current_stream(dev)
     if stream is not None:
         for f in frames:
-            f.record_stream(st)                                              # the allocator must not hand a dropped frame on while `st` still reads it
-    with torch.cuda.device(dev), torch.cuda.stream(st):
-        stage = torch.zeros(off, dtype=torch.uint8, pin_memory=True)
-        host = stage.numpy()
-        host[:HEADER_DT.itemsize] = np.frombuffer(hdr.tobytes(), np.uint8)
-        for o, arr in sections:
-            host[o:o + arr.nbytes] = arr.reshape(-1).view(np.uint8)
-        blob = stage.to(dev, non_blocking=True)                              # the call's one host -> device copy
+            f.record_stream(stream)                                          # the allocator must not hand a dropped frame on while `stream` still reads it
+    with staging.staged(off, dev, stream, zeros=True) as s:                  # zeros: the alignment gaps are defined bytes
+        staging.write_blob(s.host, hdr, sections)
+        blob = s.copy()
         n_sums = -(-block // 256)
         coef = torch.empty(64 * block, dtype=torch.int16, device=dev)
         bits = torch.empty(block, dtype=torch.int32, device=dev)
@@ -313,8 +270,8 @@ def encode(frames, quality=95, subsampling="4:2:0", rects=None, stream=None, tap
         out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)          # header + EOI + twice the worst case (stuffing) per file; the files are written back to back
         lengths = torch.empty(n, dtype=torch.int32, device=dev)
         offsets = torch.empty(n, dtype=torch.int64, device=dev)
-        lib.check(L.maf_jpeg_encode(host.ctypes.data, blob.data_ptr(), coef.data_ptr(), bits.data_ptr(), bitoff.data_ptr(), sums.data_ptr(),
-                                    packed.data_ptr(), ffcount.data_ptr(), out.data_ptr(), lengths.data_ptr(), offsets.data_ptr(), st.cuda_stream))
+        lib.check(L.maf_jpeg_encode(s.host.ctypes.data, blob.data_ptr(), coef.data_ptr(), bits.data_ptr(), bitoff.data_ptr(), sums.data_ptr(),
+                                    packed.data_ptr(), ffcount.data_ptr(), out.data_ptr(), lengths.data_ptr(), offsets.data_ptr(), s.stream.cuda_stream))
     if taps is not None:
         taps.update(coef=coef, bits=bits, bitoff=bitoff, packed=packed, jobs=jobs, header=hdr, quant=quant)
-    return EncodedBatch(out, offsets, lengths, st, (frames, stage, blob, coef, bits, bitoff, sums, packed, ffcount))
+    return EncodedBatch(out, offsets, lengths, s.stream, (frames, s.pinned, blob, coef, bits, bitoff, sums, packed, ffcount))

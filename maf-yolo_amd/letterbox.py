@@ -17,11 +17,12 @@ The geometry (scale, unpadded size, padding) is host bookkeeping with the refere
 tests/letterbox_ref.py and its uint8 INTER_AREA as restated in tests/area_ref.py, bit for bit.  No CPU fallback: CPU or non-uint8 frames raise MafError.
 """
 import math
+from functools import partial
 
 import numpy as np
 import torch
 
-from . import lib
+from . import lib, staging
 from .lib import MafError
 from .nms import NmsHandle, nms_raw
 
@@ -164,22 +165,17 @@ def area_table(n_src, n_dst):
 
 # ---------------------------------------------------------------- device
 
+_FRAME_TEXT = {      # staging.frame_list in this module's words; `what` names the entry point
+    "batch": "letterbox: a single tensor of frames is uint8 [B, h, w, 3]",
+    "none": "letterbox: no frames",
+    "not_tensor": "%(what)s runs on the HIP path only: frames must be CUDA tensors (no CPU fallback)",
+    "cpu": "%(what)s runs on the HIP path only: frames must be CUDA tensors (no CPU fallback)",
+    "type": "letterbox: frames are uint8 [h, w, 3] tensors, got %(dtype)s %(shape)s",
+    "stride": "letterbox: a frame needs pixel stride 3 and channel stride 1 (rows may have any pitch)"}
+
+
 def _frame_list(frames, what="letterbox"):
-    if torch.is_tensor(frames):
-        if frames.dim() != 4:
-            raise MafError("letterbox: a single tensor of frames is uint8 [B, h, w, 3]")
-        frames = list(frames.unbind(0))
-    frames = list(frames)
-    if not frames:
-        raise MafError("letterbox: no frames")
-    for f in frames:
-        if not torch.is_tensor(f) or not f.is_cuda:
-            raise MafError("%s runs on the HIP path only: frames must be CUDA tensors (no CPU fallback)" % what)
-        if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3:
-            raise MafError("letterbox: frames are uint8 [h, w, 3] tensors, got %s %s" % (f.dtype, tuple(f.shape)))
-        if f.stride(2) != 1 or f.stride(1) != 3:
-            raise MafError("letterbox: a frame needs pixel stride 3 and channel stride 1 (rows may have any pitch)")
-    return frames
+    return staging.frame_list(frames, _FRAME_TEXT, what)
 
 
 def _launch(frames, H, W, geoms, color, bgr):
@@ -216,9 +212,6 @@ def letterbox(frames, new_shape=640, color=(114, 114, 114), auto=True, scaleup=T
     H, W = _check_one_shape(geoms)
     imgs = _launch(frames, H, W, geoms, color, bgr)
     return imgs, [g["ret"][0] for g in geoms], [g["ret"][1] for g in geoms]
-
-
-_area_checked = False
 
 
 def _area_tables(frames, sizes):
@@ -258,18 +251,7 @@ def _area_tables(frames, sizes):
     return tab, (np.concatenate(words) if words else np.zeros(0, np.int32)), off
 
 
-def _area_library():
-    """The HIP library, with the frame struct of this binding checked against it once."""
-    global _area_checked
-    L = lib.load()
-    if not _area_checked:
-        import ctypes
-        size = (ctypes.c_int32 * 1)()
-        lib.check(L.maf_area_struct_sizes(size))
-        if size[0] != AREA_FRAME_DT.itemsize:
-            raise MafError("libmafyolo_hip.so was built for a maf_area_frame_t of %d bytes, this binding declares %d: rebuild" % (size[0], AREA_FRAME_DT.itemsize))
-        _area_checked = True
-    return L
+_area_library = partial(staging.checked_library, "area", (("maf_area_struct_sizes", 1),), AREA_FRAME_DT.itemsize, "a maf_area_frame_t")
 
 
 def resize_area(frames, sizes, stream=None):
@@ -287,18 +269,15 @@ def resize_area(frames, sizes, stream=None):
         raise MafError("resize_area: the frames of a call live on one device")
     tab, words, total = _area_tables(frames, sizes)
     L = _area_library()
-    st = stream if stream is not None else torch.cuda.current_stream(dev)
-    with torch.cuda.device(dev), torch.cuda.stream(st):
+    tab_bytes = tab.nbytes                                                # a multiple of 8: the table words behind it stay aligned
+    with staging.staged(tab_bytes + words.nbytes, dev, stream) as s:
         out = torch.empty(total, dtype=torch.uint8, device=dev)
         tab["dst"] += np.uint64(out.data_ptr())
-        tab_bytes = tab.nbytes                                            # a multiple of 8: the table words behind it stay aligned
-        stage = torch.empty(tab_bytes + words.nbytes, dtype=torch.uint8, pin_memory=True)
-        host = stage.numpy()
-        host[:tab_bytes] = tab.view(np.uint8)
-        host[tab_bytes:] = words.view(np.uint8)
-        blob = stage.to(dev, non_blocking=True)                           # the call's one host -> device copy
-        lib.check(L.maf_resize_area(host.ctypes.data, blob.data_ptr(), len(frames), host.ctypes.data + tab_bytes if words.size else None,
-                                    blob.data_ptr() + tab_bytes if words.size else None, words.size, st.cuda_stream))
+        s.host[:tab_bytes] = tab.view(np.uint8)
+        s.host[tab_bytes:] = words.view(np.uint8)
+        blob = s.copy()
+        lib.check(L.maf_resize_area(s.host.ctypes.data, blob.data_ptr(), len(frames), s.host.ctypes.data + tab_bytes if words.size else None,
+                                    blob.data_ptr() + tab_bytes if words.size else None, words.size, s.stream.cuda_stream))
     res, off = [], 0
     for nh, nw in sizes:
         res.append(out[off:off + 3 * nh * nw].view(nh, nw, 3))
@@ -344,11 +323,6 @@ def rescale_params(letterboxed_hw, src_shapes):
     return par
 
 
-def _upload(arr, dev):
-    """Host array -> device on the current stream, without a host sync (pinned staging)."""
-    return torch.from_numpy(arr).pin_memory().to(dev, non_blocking=True)
-
-
 def rescale_boxes(dets, letterboxed_hw, src_shapes, round=True):
     """Inferer.rescale(img.shape[2:], det[:, :4], img_src.shape).round() for a batch, in place on the device.  `dets` is any result form that
     convert_to_coco_format accepts: the list of [n_i, 6] tensors, the (rows, idx, count) triple of nms_raw, or an NmsHandle.  Returns `dets`."""
@@ -376,7 +350,7 @@ def rescale_boxes(dets, letterboxed_hw, src_shapes, round=True):
     rows = torch.zeros(B, md, 6, dtype=torch.float32, device=dev)
     for b, o in enumerate(dets):
         rows[b, :o.shape[0]] = o
-    cnt = _upload(np.array([int(o.shape[0]) for o in dets], np.int32), dev)
+    cnt = staging.upload(np.array([int(o.shape[0]) for o in dets], np.int32), dev)
     _rescale(rows, cnt, letterboxed_hw, src_shapes, round)
     for b, o in enumerate(dets):
         o[:, :4] = rows[b, :o.shape[0], :4]
@@ -387,7 +361,7 @@ def _rescale(rows, cnt, letterboxed_hw, src_shapes, do_round):
     B, max_det, stride = rows.shape
     if len(src_shapes) != B:
         raise MafError("rescale_boxes: %d source shapes for %d images" % (len(src_shapes), B))
-    par = _upload(rescale_params(letterboxed_hw, src_shapes), rows.device)
+    par = staging.upload(rescale_params(letterboxed_hw, src_shapes), rows.device)
     st = torch.cuda.current_stream(rows.device)
     lib.check(lib.load().maf_rescale_boxes(rows.data_ptr(), cnt.data_ptr(), B, max_det, stride, par.data_ptr(), int(bool(do_round)), st.cuda_stream))
 

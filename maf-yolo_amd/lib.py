@@ -158,6 +158,12 @@ class MafError(RuntimeError):
     pass
 
 
+def check_sizes(what, have, want, hint=""):
+    """The one comparison of what the library says a struct measures (`have`: a size or a list of sizes) with what this binding declares."""
+    if have != want:
+        raise MafError("libmafyolo_hip.so was built for %s of %s bytes, this binding declares %s: rebuild%s" % (what, have, want, hint))
+
+
 def load():
     """Load the HIP library (once). Raises MafError if it has not been built (run __graft_entry__.build())."""
     global _lib
@@ -171,9 +177,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     lib.maf_last_error.restype = C.c_char_p
     lib.maf_version.restype = C.c_int
-    if not hasattr(lib, "maf_op_size") or lib.maf_op_size() != C.sizeof(MafOp):
-        raise MafError("libmafyolo_hip.so was built for a maf_op_t of %s bytes, this binding declares %d: rebuild (__graft_entry__.build())"
-                       % (lib.maf_op_size() if hasattr(lib, "maf_op_size") else "?", C.sizeof(MafOp)))
+    check_sizes("a maf_op_t", lib.maf_op_size() if hasattr(lib, "maf_op_size") else "?", C.sizeof(MafOp), " (__graft_entry__.build())")
     lib.maf_op_launch.argtypes = [C.POINTER(MafOp), C.c_void_p]
     lib.maf_engine_create.argtypes = [C.POINTER(MafOp), C.c_int32, C.POINTER(C.c_void_p)]
     lib.maf_engine_num_ops.argtypes = [C.c_void_p]
@@ -287,8 +291,7 @@ def load():
     lib.maf_tape_rec_size.restype = C.c_int32
     lib.maf_tape_run.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
     lib.maf_tape_toggle.argtypes = [C.c_void_p, C.c_int32]
-    if lib.maf_tape_rec_size() != C.sizeof(MafTapeRec):
-        raise MafError("libmafyolo_hip.so was built for a maf_tape_rec_t of %d bytes, this binding declares %d: rebuild" % (lib.maf_tape_rec_size(), C.sizeof(MafTapeRec)))
+    check_sizes("a maf_tape_rec_t", lib.maf_tape_rec_size(), C.sizeof(MafTapeRec))
     lib.maf_letterbox.argtypes = [C.POINTER(MafLetterboxImage), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_int32, C.c_void_p, C.c_void_p]
     lib.maf_letterbox_lds_bytes.argtypes = [C.POINTER(MafLetterboxImage), C.c_int32, C.c_int32]
     lib.maf_letterbox_lds_bytes.restype = C.c_int64
@@ -299,10 +302,8 @@ def load():
     lib.maf_polygon_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.maf_mosaic_affine_paste.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.maf_augment_paste_size.restype = C.c_int32
-    if lib.maf_augment_paste_size() != C.sizeof(MafAugmentPaste):
-        raise MafError("libmafyolo_hip.so was built for a maf_augment_paste_t of %d bytes, this binding declares %d: rebuild" % (lib.maf_augment_paste_size(), C.sizeof(MafAugmentPaste)))
-    if lib.maf_augment_sample_size() != C.sizeof(MafAugmentSample):
-        raise MafError("libmafyolo_hip.so was built for a maf_augment_sample_t of %d bytes, this binding declares %d: rebuild" % (lib.maf_augment_sample_size(), C.sizeof(MafAugmentSample)))
+    check_sizes("a maf_augment_paste_t", lib.maf_augment_paste_size(), C.sizeof(MafAugmentPaste))
+    check_sizes("a maf_augment_sample_t", lib.maf_augment_sample_size(), C.sizeof(MafAugmentSample))
     lib.maf_area_struct_sizes.argtypes = [C.POINTER(C.c_int32)]
     lib.maf_resize_area.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     lib.maf_pr_state_ints.argtypes = [C.c_int32]

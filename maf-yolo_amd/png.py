@@ -22,15 +22,16 @@ interlacing, a compression or filter method other than 0, a zlib header with a p
 acTL chunk), an unknown critical chunk, a side above 65535 or 2 GiB of scanlines.  A palette index past PLTE is found on the device and
 reported as a status bit.  No CPU fallback.
 """
-import os
 import struct
 import zlib
 from collections import namedtuple
+from functools import partial
 
 import numpy as np
 
-from . import lib
+from . import lib, staging
 from .lib import MafError
+from .staging import align as _align, file_bytes
 
 
 class PngUnsupported(MafError):
@@ -53,14 +54,6 @@ _STATUS_TEXT = ((STATUS_INPUT_EXHAUSTED, "a deflate stream that ends early"), (S
                 (STATUS_NO_CODE, "bits that match no Huffman code"), (STATUS_DISTANCE_TOO_FAR, "a distance that reaches before the start of the output"),
                 (STATUS_TOO_MANY_BYTES, "more scanline bytes than the image holds"), (STATUS_TOO_FEW_BYTES, "fewer scanline bytes than the image holds"),
                 (STATUS_BAD_FILTER, "a filter type above 4"), (STATUS_BAD_PALETTE_INDEX, "a palette index past PLTE"))
-
-
-def file_bytes(data):
-    """The bytes of a file given as a path, or of a bytes-like object (frames.py reads every file once with it)."""
-    if isinstance(data, (str, os.PathLike)):
-        with open(data, "rb") as f:
-            return f.read()
-    return bytes(data)
 
 
 def parse(data):
@@ -170,10 +163,6 @@ STREAM_PAD = 64               # zero bytes the host appends to the streams (the 
 STAGE_INFLATE, STAGE_UNFILTER, STAGE_CONVERT, STAGE_ALL = 1, 2, 4, 7
 
 
-def _align(x, a=16):
-    return (x + a - 1) // a * a
-
-
 def build_blob(infos):
     """Everything the device needs for one call, in one byte array: header | image table | palettes (B, G, R, 0 per entry) | the zlib streams of
     every image (IDAT payloads concatenated, chunk framing removed) + STREAM_PAD zeros.  -> (header record, image table, palette entries)."""
@@ -198,28 +187,20 @@ def build_blob(infos):
         rows += _align(info.height * info.rowbytes)
         outb += _align(3 * info.width * info.height)
     palette = np.concatenate(pals) if pals else np.zeros((0, 4), np.uint8)
-    hdr = np.zeros(1, HEADER_DT)[0]
-    off = _align(HEADER_DT.itemsize)
+    hdr, off = staging.blob_layout(HEADER_DT, (("images_off", images), ("palette_off", palette)))
     hdr["n_images"], hdr["n_palette"] = B, npal
-    hdr["images_off"] = off
-    off = _align(off + images.nbytes)
-    hdr["palette_off"] = off
-    off = _align(off + palette.nbytes)
     hdr["stream_off"] = off
     hdr["stream_bytes"] = _align(at + STREAM_PAD)            # a multiple of 8: the bit reader loads aligned 8-byte words
     hdr["total_bytes"] = off + _align(at + STREAM_PAD)
     hdr["inflated_bytes"], hdr["rows_bytes"], hdr["out_bytes"] = inf, rows, outb
-    if hdr["total_bytes"] >= 2 ** 31 or B > 65535:
+    if hdr["total_bytes"] >= staging.MAX_BLOB or B > staging.MAX_FILES:
         raise MafError("png: decode() takes up to 65535 files and 2 GiB of file bytes per call")
     return hdr, images, palette
 
 
 def fill_blob(buf, hdr, images, palette, datas, infos):
     """Write the sections of build_blob into `buf` (a uint8 array of hdr.total_bytes: the pinned staging buffer)."""
-    buf[:HEADER_DT.itemsize] = np.frombuffer(hdr.tobytes(), np.uint8)
-    for name, arr in (("images_off", images), ("palette_off", palette)):
-        o = int(hdr[name])
-        buf[o:o + arr.nbytes] = arr.reshape(-1).view(np.uint8)
+    staging.write_blob(buf, hdr, (("images_off", images), ("palette_off", palette)))
     q = int(hdr["stream_off"])
     for d, info in zip(datas, infos):
         for s, e in info.idat:
@@ -228,30 +209,8 @@ def fill_blob(buf, hdr, images, palette, datas, infos):
     buf[q:] = 0                                              # at least STREAM_PAD zero bytes
 
 
-_lib_checked = False
-
-
-def _library():
-    """The HIP library, with the struct sizes of this binding checked against it once."""
-    global _lib_checked
-    L = lib.load()
-    if not _lib_checked:
-        import ctypes
-        sizes = (ctypes.c_int32 * 2)()
-        lib.check(L.maf_png_struct_sizes(sizes))
-        if list(sizes) != [HEADER_DT.itemsize, IMAGE_DT.itemsize]:
-            raise MafError("libmafyolo_hip.so was built for maf_png_* structs of %s bytes, this binding declares %s: rebuild"
-                           % (list(sizes), [HEADER_DT.itemsize, IMAGE_DT.itemsize]))
-        _lib_checked = True
-    return L
-
-
-def _name(f, i):
-    return "file %d (%s)" % (i, os.fspath(f)) if isinstance(f, (str, os.PathLike)) else "file %d" % i
-
-
-def status_text(word):
-    return ", ".join(t for bit, t in _STATUS_TEXT if word & bit) or "status 0x%x" % word
+_library = partial(staging.checked_library, "png", (("maf_png_struct_sizes", 2),), [HEADER_DT.itemsize, IMAGE_DT.itemsize], "maf_png_* structs")
+status_text = partial(staging.status_text, _STATUS_TEXT)
 
 
 def decode(files, device=None, stream=None, check=True, stages=STAGE_ALL, taps=None):
@@ -263,47 +222,16 @@ def decode(files, device=None, stream=None, check=True, stages=STAGE_ALL, taps=N
     `taps`: a dict that receives the intermediate buffers (the inflated scanlines, the unfiltered rows, the image table) — tests and the probe.
     `stages`: for the probe and the tests only.  A mask without STAGE_INFLATE neither clears the status words nor fills the buffers the later
     stages read (they are fresh allocations here), so the frames and the status of such a call mean nothing; decode with STAGE_ALL."""
-    import torch
-    files = list(files)
-    if not files:
-        raise MafError("png.decode: no files")
-    dev = torch.device("cuda" if device is None else device)
-    if dev.type != "cuda":
-        raise MafError("png.decode runs on the HIP path only (no CPU fallback): device %s" % dev)
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    datas, infos = [], []
-    for i, f in enumerate(files):
-        d = file_bytes(f)
-        try:
-            infos.append(parse(d))
-        except MafError as e:
-            raise type(e)("%s: %s" % (_name(f, i), e)) from None
-        datas.append(d)
-    hdr, images, palette = build_blob(infos)
-    L = _library()
-    st = stream if stream is not None else torch.cuda.current_stream(dev)
-    with torch.cuda.device(dev), torch.cuda.stream(st):
-        stage = torch.empty(int(hdr["total_bytes"]), dtype=torch.uint8, pin_memory=True)
-        host = stage.numpy()
-        fill_blob(host, hdr, images, palette, datas, infos)
-        blob = stage.to(dev, non_blocking=True)                                  # the call's one host -> device copy
-        inflated = torch.empty(int(hdr["inflated_bytes"]), dtype=torch.uint8, device=dev)
-        rows = torch.empty(int(hdr["rows_bytes"]), dtype=torch.uint8, device=dev)
-        out = torch.empty(int(hdr["out_bytes"]), dtype=torch.uint8, device=dev)
-        status = torch.empty(len(files), dtype=torch.int32, device=dev)
-        lib.check(L.maf_png_decode(host.ctypes.data, blob.data_ptr(), inflated.data_ptr(), rows.data_ptr(), out.data_ptr(), status.data_ptr(),
-                                   int(stages), st.cuda_stream))
-        frames = []
-        for im in images:
-            o, h, w = int(im["out_off"]), int(im["h"]), int(im["w"])
-            frames.append(out[o:o + 3 * h * w].view(h, w, 3))
-        if taps is not None:
-            taps.update(inflated=inflated, rows=rows, images=images, status=status, header=hdr)
-        if not check:
-            return frames, status
-        words = status.tolist()                                                  # the one synchronisation (it also keeps `stage` alive until the copy is done)
-    bad = [(i, w) for i, w in enumerate(words) if w]
-    if bad:
-        raise MafError("png.decode: " + "; ".join("%s: %s (status 0x%x)" % (_name(files[i], i), status_text(w), w) for i, w in bad))
-    return frames
+    def build(datas, infos):
+        hdr, images, palette = build_blob(infos)
+        return hdr, images, lambda host: fill_blob(host, hdr, images, palette, datas, infos)
+
+    def launch(L, s, blob, hdr, out, status):
+        import torch
+        inflated = torch.empty(int(hdr["inflated_bytes"]), dtype=torch.uint8, device=s.dev)
+        rows = torch.empty(int(hdr["rows_bytes"]), dtype=torch.uint8, device=s.dev)
+        lib.check(L.maf_png_decode(s.host.ctypes.data, blob.data_ptr(), inflated.data_ptr(), rows.data_ptr(), out.data_ptr(), status.data_ptr(),
+                                   int(stages), s.stream.cuda_stream))
+        return dict(inflated=inflated, rows=rows)
+
+    return staging.decode_files("png.decode", files, parse, build, _library, launch, _STATUS_TEXT, True, device, stream, check, taps)

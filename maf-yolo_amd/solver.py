@@ -52,7 +52,7 @@ class GradScaler(torch.amp.GradScaler):
         if ent is None or ent[0] != sig:
             import ctypes as C
             from . import lib
-            assert C.sizeof(lib.MafRangeDesc) == lib.load().maf_range_desc_size()
+            lib.check_sizes("a maf_range_desc_t", lib.load().maf_range_desc_size(), C.sizeof(lib.MafRangeDesc))
             merged = []
             for ptr, n in sorted(set(grads)):
                 if merged and merged[-1][0] + 4 * merged[-1][1] == ptr:
@@ -132,7 +132,7 @@ class NativeSGD(torch.optim.SGD):
         dev = ents[0][0].device
         sig = tuple((p.data_ptr(), g.data_ptr(), b.data_ptr() if b is not None else 0, gi) for p, g, b, gi in ents)
         if sig != self._maf_sig:
-            assert C.sizeof(lib.MafSgdDesc) == lib.load().maf_sgd_desc_size()
+            lib.check_sizes("a maf_sgd_desc_t", lib.load().maf_sgd_desc_size(), C.sizeof(lib.MafSgdDesc))
             arr = (lib.MafSgdDesc * len(ents))()
             blk = 0
             for e, (p, g, b, gi) in zip(arr, ents):
@@ -280,7 +280,7 @@ class ModelEMA:
                 for e, (a, b) in zip(arr, pairs):
                     e.dst, e.src, e.total, e.block0 = a.data_ptr(), b.data_ptr(), a.numel(), blk
                     blk += -(-a.numel() // 1024)
-                assert C.sizeof(lib.MafEmaDesc) == lib.load().maf_ema_desc_size()
+                lib.check_sizes("a maf_ema_desc_t", lib.load().maf_ema_desc_size(), C.sizeof(lib.MafEmaDesc))
                 if pairs:
                     self._table = (torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dst[0].device), len(pairs), blk, dst[0].device)
         return bool(self._table)

@@ -443,7 +443,7 @@ def begin_step(plan, dev):
             d.kind, d.dtype, d.Cout, d.Cin, d.taps, d.transpose = f["kind"], f["dtype"], f["Cout"], f["Cin"], f["taps"], f["transpose"]
             d.CT, d.steps, d.Kp, d.flip, d.block0 = f["CT"], f["steps"], f["Kp"], f["flip"], blk
             blk += -(-f["total"] // 1024)
-        assert C.sizeof(lib.MafPackDesc) == lib.load().maf_pack_desc_size()
+        lib.check_sizes("a maf_pack_desc_t", lib.load().maf_pack_desc_size(), C.sizeof(lib.MafPackDesc))
         plan.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
         plan.nblocks = blk
         plan.dirty = False
