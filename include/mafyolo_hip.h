@@ -195,6 +195,15 @@ int maf_version(void);
 /* sizeof(maf_op_t) as this library was compiled: a binding checks its own struct against it at load time (a stub that is short of
  * fields would make maf_engine_create read past every element of the op array). */
 int maf_op_size(void);
+/* The signatures of this header as the library was compiled (csrc/abi.hip): entry i < maf_abi_count() is an exported function's name and its signature as a
+ * string, one character for the return type, ':', one character per parameter — v void (return only), s const char*, p any other pointer (maf_stream_t
+ * included), f float, d double, i int32_t / int, l int64_t; maf_nms_workspace_bytes is "l:iii".  The compiler derives the strings from the prototypes
+ * above and below and refuses any other type, so a binding that sets its argument types from this table (maf-yolo_amd/lib.py does) follows a changed
+ * prototype with the next build instead of passing shifted arguments.  Every function of this header is in the table, these three included; NULL
+ * for an index out of range. */
+int32_t maf_abi_count(void);
+const char* maf_abi_name(int32_t i);
+const char* maf_abi_signature(int32_t i);
 /* Bytes of one 32-mid-channel block record of MAF_OP_BOTTLENECK for kernel size k and c = Cin = Cout channels. */
 int64_t maf_bottleneck_record_bytes(int32_t k, int32_t Cin, int32_t Cout);
 /* MAF_OP_BOTTLENECK with nc = C3 > 0 (the closing 1x1 of the RepHDW block behind it): bytes of aux[0]'s record for c channels per concat slot and nsrc

@@ -3,7 +3,8 @@
 // train-form graph here is ~900 short kernels, and issuing them one by one from autograd Functions costs the host as long as the step takes
 // on the device.  A record is (entry point, stream selector, argument words); the entry points are the ordinary exported functions of this
 // library, called through their own prototypes — the argument conversion below is derived by the compiler from the declarations in the
-// header, so a changed signature cannot go unnoticed.  Host code only: no kernel lives here.
+// header, so a changed signature cannot go unnoticed.  (csrc/abi.hip derives the Python binding's argument types from the same declarations, for the whole
+// ABI; the table here is the tape-able subset, and its order defines the function ids.)  Host code only: no kernel lives here.
 #include <cstring>
 #include <type_traits>
 #include <utility>

@@ -141,7 +141,7 @@ class MafOp(C.Structure):
                 ("out_pairs", C.c_int32), ("reserved0", C.c_int32)]
 
 
-EXPORTS = ["maf_last_error", "maf_version", "maf_op_size", "maf_op_launch", "maf_engine_create", "maf_engine_num_ops",
+EXPORTS = ["maf_abi_count", "maf_abi_name", "maf_abi_signature", "maf_last_error", "maf_version", "maf_op_size", "maf_op_launch", "maf_engine_create", "maf_engine_num_ops",
            "maf_engine_run", "maf_engine_run_filtered", "maf_engine_run_graph", "maf_engine_run_timed", "maf_engine_destroy", "maf_nms_workspace_bytes", "maf_nms", "maf_nms_ex", "maf_nms_debug", "maf_pack_w1x1_bytes", "maf_pack_w1x1", "maf_pack_dw", "maf_pack_batch", "maf_pack_desc_size", "maf_ema_update", "maf_ema_desc_size", "maf_sgd_update", "maf_sgd_desc_size", "maf_nonfinite_check", "maf_range_desc_size", "maf_maxpool_forward", "maf_maxpool_backward", "maf_upsample2x_forward", "maf_upsample2x_backward", "maf_zero", "maf_grad_fold", "maf_add_sub2", "maf_colsum", "maf_dw_wgrad", "maf_dw_wgrad31", "maf_stem_train", "maf_image_to_nhwc8", "maf_bottleneck_record_bytes", "maf_bottleneck_tail_record_bytes", "maf_bottleneck_tail_supported", "maf_conv1dw_record_bytes", "maf_head_tail_record_bytes", "maf_stem2_record_bytes", "maf_conv3s2_lds_record_bytes", "maf_mprep_lds_record_bytes", "maf_mprep_wreg_record_bytes", "maf_conv3s2_wreg_record_bytes", "maf_conv1x1_stats_supported", "maf_coco_rows", "maf_conv1x1_wgrad", "maf_conv_wgrad", "maf_bn_forward", "maf_bn_backward", "maf_bn_backward_acc", "maf_set_deterministic", "maf_dw_branches", "maf_dw_branches_stats", "maf_bn_forward_ex", "maf_bn_replicas", "maf_bn_stats", "maf_bn_sum_forward", "maf_bn_sum_forward_stats", "maf_bn_sum_backward", "maf_tal_targets", "maf_tal_assign", "maf_atss_assign", "maf_loss_partial_rows", "maf_loss_decode", "maf_loss_terms",
            "maf_detect_join", "maf_detect_join_backward", "maf_nhwc_sum", "maf_stream_fork", "maf_stream_join", "maf_tape_fn_id", "maf_tape_fn_nargs", "maf_tape_rec_size", "maf_tape_run", "maf_tape_toggle",
            "maf_stream_create_masked", "maf_stream_destroy", "maf_letterbox", "maf_letterbox_lds_bytes", "maf_rescale_boxes",
@@ -164,6 +164,53 @@ def check_sizes(what, have, want, hint=""):
         raise MafError("libmafyolo_hip.so was built for %s of %s bytes, this binding declares %s: rebuild%s" % (what, have, want, hint))
 
 
+# a character of a signature of the library's table (include/mafyolo_hip.h, maf_abi_signature) -> the ctypes type that passes it
+ABI_KINDS = {"v": None, "s": C.c_char_p, "p": C.c_void_p, "f": C.c_float, "d": C.c_double, "i": C.c_int32, "l": C.c_int64}
+# Pointer parameters that ctypes is to type-check and convert (a structure passed by reference, an array, None) instead of taking an address: function ->
+# {slot: type}.  The only thing about a signature that is written here; everything else comes from the library.
+_INT32_OUT = {0: C.POINTER(C.c_int32)}
+TYPED_POINTERS = {
+    "maf_op_launch": {0: C.POINTER(MafOp)},
+    "maf_engine_create": {0: C.POINTER(MafOp), 2: C.POINTER(C.c_void_p)},
+    "maf_engine_run_timed": {4: C.POINTER(C.c_float)},
+    "maf_nms_debug": {0: C.POINTER(C.c_uint64)},
+    "maf_sgd_update": {4: C.POINTER(C.c_double), 5: C.POINTER(C.c_double), 6: C.POINTER(C.c_double), 7: C.POINTER(C.c_int32)},
+    "maf_stream_create_masked": {2: C.POINTER(C.c_void_p)},
+    "maf_tape_run": {5: C.POINTER(C.c_int32)},
+    "maf_letterbox": {0: C.POINTER(MafLetterboxImage), 5: C.POINTER(C.c_uint8)},
+    "maf_letterbox_lds_bytes": {0: C.POINTER(MafLetterboxImage)},
+    "maf_area_struct_sizes": _INT32_OUT, "maf_jpeg_struct_sizes": _INT32_OUT, "maf_jpeg_progressive_struct_sizes": _INT32_OUT,
+    "maf_jpeg_encode_struct_sizes": _INT32_OUT, "maf_png_struct_sizes": _INT32_OUT,
+    "maf_timer_create": {0: C.POINTER(C.c_void_p)},
+    "maf_timer_elapsed_ms": {1: C.POINTER(C.c_float)},
+}
+
+
+def bind(lib):
+    """Set restype and argtypes of every exported function from the signature table inside the library (csrc/abi.hip: derived from the header's
+    prototypes by the compiler), with the pointers of TYPED_POINTERS refined."""
+    if not hasattr(lib, "maf_abi_count"):
+        raise MafError("libmafyolo_hip.so has no signature table (maf_abi_count): it was built before this binding took its types from the library: rebuild "
+                       "(__graft_entry__.build())")
+    lib.maf_abi_count.restype, lib.maf_abi_count.argtypes = C.c_int32, []
+    for fn in (lib.maf_abi_name, lib.maf_abi_signature):
+        fn.restype, fn.argtypes = C.c_char_p, [C.c_int32]
+    table = {lib.maf_abi_name(i).decode(): lib.maf_abi_signature(i).decode() for i in range(lib.maf_abi_count())}
+    odd = sorted((set(table) ^ set(EXPORTS)) | (set(TYPED_POINTERS) - set(table)))
+    if odd:
+        raise MafError("libmafyolo_hip.so's signature table, lib.EXPORTS and lib.TYPED_POINTERS do not name the same functions: %s: rebuild, or bring "
+                       "csrc/abi.hip and lib.py in line with include/mafyolo_hip.h" % ", ".join(odd))
+    for name, sig in table.items():
+        ret, params = sig.split(":")
+        types = [ABI_KINDS[k] for k in params]
+        for slot, typ in TYPED_POINTERS.get(name, {}).items():
+            if slot >= len(params) or params[slot] != "p":
+                raise MafError("lib.TYPED_POINTERS types argument %d of %s, which the library declares as '%s' (no pointer there)" % (slot, name, sig))
+            types[slot] = typ
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = ABI_KINDS[ret], types
+
+
 def load():
     """Load the HIP library (once). Raises MafError if it has not been built (run __graft_entry__.build())."""
     global _lib
@@ -175,169 +222,11 @@ def load():
         raise MafError("libmafyolo_hip.so not found at %s — the HIP extension is not built; "
                        "run `python -c 'import __graft_entry__ as g; g.build()'` (there is no CPU fallback)" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    lib.maf_last_error.restype = C.c_char_p
-    lib.maf_version.restype = C.c_int
-    check_sizes("a maf_op_t", lib.maf_op_size() if hasattr(lib, "maf_op_size") else "?", C.sizeof(MafOp), " (__graft_entry__.build())")
-    lib.maf_op_launch.argtypes = [C.POINTER(MafOp), C.c_void_p]
-    lib.maf_engine_create.argtypes = [C.POINTER(MafOp), C.c_int32, C.POINTER(C.c_void_p)]
-    lib.maf_engine_num_ops.argtypes = [C.c_void_p]
-    lib.maf_engine_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.maf_engine_run_graph.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.maf_engine_run_timed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
-    lib.maf_engine_destroy.argtypes = [C.c_void_p]
-    lib.maf_engine_destroy.restype = None
-    lib.maf_engine_run_filtered.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double]
-    lib.maf_nms_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    lib.maf_nms_workspace_bytes.restype = C.c_int64
-    lib.maf_nms.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_int32,
-                            C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                            C.c_void_p]
-    lib.maf_nms_ex.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_int32,
-                               C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.maf_nms_debug.argtypes = [C.POINTER(C.c_uint64)]
-    lib.maf_conv1x1_wgrad.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.maf_conv_wgrad.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_int32] * 10 + [C.c_void_p, C.c_void_p]
-    lib.maf_tal_assign.argtypes = ([C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.c_int32] * 5 + [C.c_float] * 3 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_float]
-                                   + [C.c_void_p] * 4)
-    lib.maf_atss_assign.argtypes = [C.c_void_p] * 5 + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p, C.c_float, C.c_float] + [C.c_void_p] * 4
-    lib.maf_loss_partial_rows.argtypes = [C.c_int32] * 3
-    lib.maf_loss_partial_rows.restype = C.c_int64
-    lib.maf_loss_decode.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] * 2
-    lib.maf_loss_terms.argtypes = [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_float] * 3 + [C.c_void_p] * 6
-    lib.maf_tal_targets.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 4
-    lib.maf_bn_forward.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.maf_bn_backward.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.maf_bn_backward_acc.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
-    lib.maf_set_deterministic.argtypes = [C.c_int32]
-    lib.maf_dw_branches.argtypes = [C.c_void_p] * 5 + [C.c_int32] * 8 + [C.c_void_p]
-    lib.maf_dw_branches_stats.argtypes = [C.c_void_p] * 5 + [C.c_int32] * 7 + [C.c_void_p, C.c_int32, C.c_void_p]
-    lib.maf_bn_forward_ex.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
-    lib.maf_bn_stats.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
-    lib.maf_bn_sum_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.maf_bn_sum_forward_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
-                                             C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
-    lib.maf_bn_sum_backward.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-    lib.maf_bn_replicas.argtypes = [C.c_int32, C.c_int32]
-    lib.maf_bn_replicas.restype = C.c_int32
-    lib.maf_conv1x1_stats_supported.argtypes = [C.c_int32, C.c_int32]
-    lib.maf_conv1x1_stats_supported.restype = C.c_int
-    lib.maf_coco_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.maf_conv1dw_record_bytes.argtypes = [C.c_int32] * 2
-    lib.maf_conv1dw_record_bytes.restype = C.c_int64
-    lib.maf_head_tail_record_bytes.argtypes = [C.c_int32]
-    lib.maf_head_tail_record_bytes.restype = C.c_int64
-    lib.maf_stem2_record_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    lib.maf_stem2_record_bytes.restype = C.c_int64
-    lib.maf_conv3s2_lds_record_bytes.argtypes = [C.c_int32, C.c_int32]
-    lib.maf_conv3s2_lds_record_bytes.restype = C.c_int64
-    lib.maf_mprep_lds_record_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    lib.maf_mprep_lds_record_bytes.restype = C.c_int64
-    lib.maf_mprep_wreg_record_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    lib.maf_mprep_wreg_record_bytes.restype = C.c_int64
-    lib.maf_conv3s2_wreg_record_bytes.argtypes = [C.c_int32, C.c_int32]
-    lib.maf_conv3s2_wreg_record_bytes.restype = C.c_int64
-    lib.maf_bottleneck_record_bytes.argtypes = [C.c_int32] * 3
-    lib.maf_bottleneck_record_bytes.restype = C.c_int64
-    lib.maf_bottleneck_tail_record_bytes.argtypes = [C.c_int32] * 3
-    lib.maf_bottleneck_tail_record_bytes.restype = C.c_int64
-    lib.maf_bottleneck_tail_supported.argtypes = [C.c_int32] * 4
-    lib.maf_pack_w1x1_bytes.argtypes = [C.c_int32] * 5
-    lib.maf_pack_w1x1_bytes.restype = C.c_int64
-    lib.maf_pack_w1x1.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.maf_pack_dw.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.maf_pack_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
-    lib.maf_pack_desc_size.argtypes = []
-    lib.maf_ema_update.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p]
-    lib.maf_ema_desc_size.argtypes = []
-    lib.maf_sgd_update.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32),
-                                   C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.maf_sgd_desc_size.argtypes = []
-    lib.maf_nonfinite_check.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.maf_range_desc_size.argtypes = []
-    lib.maf_zero.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
-    lib.maf_grad_fold.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-    lib.maf_upsample2x_forward.argtypes = [C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p, C.c_int32, C.c_void_p]
-    lib.maf_upsample2x_backward.argtypes = [C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p, C.c_int32, C.c_void_p]
-    lib.maf_add_sub2.argtypes = [C.c_void_p, C.c_int32, C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p]
-    lib.maf_colsum.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.maf_maxpool_forward.argtypes = [C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.maf_maxpool_backward.argtypes = [C.c_void_p, C.c_int32, C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p, C.c_int32, C.c_void_p]
-    lib.maf_pack_desc_size.restype = C.c_int32
-    lib.maf_ema_desc_size.restype = C.c_int32
-    lib.maf_sgd_desc_size.restype = C.c_int32
-    lib.maf_range_desc_size.restype = C.c_int32
-    lib.maf_dw_wgrad.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.maf_image_to_nhwc8.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.maf_stem_train.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.maf_dw_wgrad31.argtypes = [C.c_void_p, C.c_int32] * 4 + [C.c_int32] * 5 + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p]
-    lib.maf_detect_join.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 3
-    lib.maf_detect_join_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_void_p]
-    lib.maf_nhwc_sum.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-    lib.maf_stream_fork.argtypes = [C.c_void_p, C.c_void_p]
-    lib.maf_stream_join.argtypes = [C.c_void_p, C.c_void_p]
-    lib.maf_stream_create_masked.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
-    lib.maf_stream_destroy.argtypes = [C.c_void_p]
-    lib.maf_tape_fn_id.argtypes = [C.c_char_p]
-    lib.maf_tape_fn_id.restype = C.c_int32
-    lib.maf_tape_fn_nargs.argtypes = [C.c_int32]
-    lib.maf_tape_fn_nargs.restype = C.c_int32
-    lib.maf_tape_rec_size.restype = C.c_int32
-    lib.maf_tape_run.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-    lib.maf_tape_toggle.argtypes = [C.c_void_p, C.c_int32]
+    bind(lib)
+    check_sizes("a maf_op_t", lib.maf_op_size(), C.sizeof(MafOp), " (__graft_entry__.build())")
     check_sizes("a maf_tape_rec_t", lib.maf_tape_rec_size(), C.sizeof(MafTapeRec))
-    lib.maf_letterbox.argtypes = [C.POINTER(MafLetterboxImage), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_int32, C.c_void_p, C.c_void_p]
-    lib.maf_letterbox_lds_bytes.argtypes = [C.POINTER(MafLetterboxImage), C.c_int32, C.c_int32]
-    lib.maf_letterbox_lds_bytes.restype = C.c_int64
-    lib.maf_rescale_boxes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.maf_augment_resize.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.maf_mosaic_affine.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.maf_augment_sample_size.restype = C.c_int32
-    lib.maf_polygon_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.maf_mosaic_affine_paste.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.maf_augment_paste_size.restype = C.c_int32
     check_sizes("a maf_augment_paste_t", lib.maf_augment_paste_size(), C.sizeof(MafAugmentPaste))
     check_sizes("a maf_augment_sample_t", lib.maf_augment_sample_size(), C.sizeof(MafAugmentSample))
-    lib.maf_area_struct_sizes.argtypes = [C.POINTER(C.c_int32)]
-    lib.maf_resize_area.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-    lib.maf_pr_state_ints.argtypes = [C.c_int32]
-    lib.maf_pr_state_ints.restype = C.c_int64
-    lib.maf_pr_out_doubles.argtypes = [C.c_int32, C.c_int32]
-    lib.maf_pr_out_doubles.restype = C.c_int64
-    lib.maf_pr_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int64]
-    lib.maf_pr_workspace_bytes.restype = C.c_int64
-    lib.maf_pr_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
-                                 C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
-                                 C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    lib.maf_pr_curves.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
-                                  C.c_void_p, C.c_void_p]
-    lib.maf_coco_append.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.maf_coco_match.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                   C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                   C.c_void_p]
-    lib.maf_coco_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p]
-    lib.maf_jpeg_struct_sizes.argtypes = [C.POINTER(C.c_int32)]
-    lib.maf_jpeg_progressive_struct_sizes.argtypes = [C.POINTER(C.c_int32)]
-    lib.maf_jpeg_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.maf_jpeg_encode_struct_sizes.argtypes = [C.POINTER(C.c_int32)]
-    lib.maf_jpeg_encode.argtypes = [C.c_void_p] * 12
-    lib.maf_png_struct_sizes.argtypes = [C.POINTER(C.c_int32)]
-    lib.maf_png_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.maf_timer_create.argtypes = [C.POINTER(C.c_void_p)]
-    lib.maf_timer_start.argtypes = [C.c_void_p, C.c_void_p]
-    lib.maf_timer_stop.argtypes = [C.c_void_p, C.c_void_p]
-    lib.maf_timer_elapsed_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-    lib.maf_timer_destroy.argtypes = [C.c_void_p]
-    lib.maf_timer_destroy.restype = None
     _lib = lib
     return lib
 

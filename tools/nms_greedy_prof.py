@@ -24,7 +24,6 @@ for _ in range(3):
 torch.cuda.synchronize()
 buf = (C.c_uint64 * 8)()
 L = lib.load()
-L.maf_nms_debug.argtypes = [C.POINTER(C.c_uint64)]
 lib.check(L.maf_nms_debug(buf))
 v = list(buf)
 mhz = 100.0          # s_memtime / readcyclecounter ticks: 100 MHz constant clock on gfx950
