@@ -899,7 +899,10 @@ int maf_coco_accumulate(const int64_t* cat_keys, const int32_t* rank, const uint
  *            whole MCUs (pitch 8 * blocks per row).
  *   COLOR    jdsample.c h2v1_fancy_upsample / h2v2_fancy_upsample (the box replication of h2v1_upsample / h2v2_upsample where the chroma
  *            plane is at most 2 samples wide), the edge rules of jdmainct.c, jdcolor.c ycc_rgb_convert's 16-bit tables -> uint8 [h][w][3]
- *            BGR at out + out_off; a one-component file writes its gray value three times.
+ *            BGR at out + out_off; a one-component file writes its gray value three times.  An image whose `orientation` is 2 to 8 is
+ *            written through that EXIF orientation instead: the stored pixel (x, y) goes to (x', y') of a frame of w x h (2 to 4) or h x w
+ *            (5 to 8) pixels, x' = x or w - 1 - x (orientations 2, 3, 7, 8), y' = y or h - 1 - y (3, 4, 6, 7), the two exchanged for 5 to
+ *            8; the same 3 * w * h bytes at out + out_off (rules restated in tests/jpeg_orientation_ref.py).
  *
  * A Huffman table set is 4 tables (DC 0, DC 1, AC 0, AC 1) of MAF_JPEG_HUFF_TABLE_BYTES: look uint16 [512] (length << 8 | symbol for every
  * 9-bit prefix that starts with a code of at most 9 bits, else 0), maxcode int32 [18] (-1: no code of that length), valoff int32 [18]
@@ -950,7 +953,8 @@ typedef struct {
     int32_t mcux, mcuy;                      /* ceil(w / (8 hs)), ceil(h / (8 vs)) */
     int32_t quant;                           /* index of the image's first quantisation table */
     int32_t dc_tab[3], ac_tab[3];            /* per component: table 0 or 1 of the set */
-    int32_t reserved[2];
+    int32_t orientation;                     /* 0 or 1: the stored grid; 2 to 8: the frame is written through that EXIF orientation (for 5 to 8 it is [w][h][3]) */
+    int32_t reserved;
 } maf_jpeg_image_t;
 typedef struct {
     int64_t begin, end;                      /* byte range of the interval inside the scan buffer (markers excluded) */
@@ -1032,8 +1036,8 @@ int maf_jpeg_encode(const void* blob_host, const void* blob_dev, int16_t* coef, 
 
 /* ------------------------------------------------------------------------------------------------------------------------------------
  * PNG decoding on the device (csrc/png_decode.hip): what cv2.imread (IMREAD_COLOR: libpng with png_set_strip_16, png_set_strip_alpha,
- * png_set_palette_to_rgb, png_set_expand_gray_1_2_4_to_8, png_set_gray_to_rgb, png_set_bgr) returns for a non-interlaced file, bit for
- * bit; the rules are those of tests/png_ref.py.  The host walks the chunks (maf-yolo_amd/png.py: CRC-32 of the critical chunks, IHDR,
+ * png_set_palette_to_rgb, png_set_expand_gray_1_2_4_to_8, png_set_gray_to_rgb, png_set_bgr) returns for a non-interlaced or an Adam7 file,
+ * bit for bit; the rules are those of tests/png_ref.py and tests/png_adam7_ref.py.  The host walks the chunks (maf-yolo_amd/png.py: CRC-32 of the critical chunks, IHDR,
  * PLTE, the zlib header) and hands over ONE byte blob, copied to the device as it is: maf_png_header_t | maf_png_image_t [n_images] |
  * palette entries uint8 [n_palette][4] (B, G, R, 0) | the zlib streams of every image (its IDAT payloads concatenated, chunk framing
  * removed) followed by at least MAF_PNG_STREAM_PAD zero bytes.
@@ -1045,6 +1049,13 @@ int maf_jpeg_encode(const void* blob_host, const void* blob_dev, int16_t* coef, 
  *   UNFILTER  PNG filter types 0 to 4 undone, lane k of a wave on row y0 + k one pixel behind lane k - 1 -> uint8 [h][rowbytes] at rows +
  *             rows_off.
  *   CONVERT   the conversion table of maf-yolo_amd/png.py -> uint8 [h][w][3] BGR at out + out_off.
+ * An image with interlace = 1 (Adam7; PNG 1.2, 8.2) rides in the same launches.  Pass p = 0 .. 6 holds the pixels (x0 + i dx, y0 + j dy),
+ * (x0, y0, dx, dy) = (0,0,8,8) (4,0,8,8) (0,4,4,8) (2,0,4,4) (0,2,2,4) (1,0,2,2) (0,1,1,2), as a sub-image of pw = ceil((w - x0) / dx) by
+ * ph = ceil((h - y0) / dy) pixels with rows of prb = ceil(pw * channels * depth / 8) bytes; a pass with pw or ph 0 is absent.  INFLATE
+ * produces the sum of ph * (1 + prb) bytes; UNFILTER (a grid of images x 7 when the call holds such an image) undoes every pass as a filter
+ * chain of its own, its first row with zeros above it, and writes the sub-images back to back at rows + rows_off, the sum of ph * prb bytes
+ * (for depths below 8 that can exceed h * rowbytes); CONVERT gathers pixel (x, y) from the pass that (x & 7, y & 7) names.  The kernels derive
+ * the geometry from w, h, depth and ctype; the blob has no section for it.
  * Bounded by construction: every input byte index is clamped into the stream section and compared with the image's stream_end, past which
  * the reader feeds zeros; every output index is compared with inflated_size; every distance with the bytes produced so far; every loop has
  * a bound the host validated or a constant one.  A malformed stream ends with bits of status[image] (MAF_PNG_ST_*) and a zero-filled
@@ -1079,9 +1090,9 @@ typedef struct {
     int32_t depth, ctype;                    /* IHDR: 1 / 2 / 4 / 8 / 16 and 0 gray, 2 RGB, 3 palette, 4 gray + alpha, 6 RGBA */
     int32_t rowbytes;                        /* ceil(w * channels * depth / 8) */
     int32_t bpp;                             /* the filters' byte distance: max(1, channels * depth / 8) */
-    int32_t inflated_size;                   /* h * (1 + rowbytes), below 2^31 */
+    int32_t inflated_size;                   /* h * (1 + rowbytes), Adam7: the sum of ph * (1 + prb) over the non-empty passes; below 2^31 */
     int32_t pal, pal_n;                      /* ctype 3: first palette entry and their number (1 to 256) */
-    int32_t reserved;
+    int32_t interlace;                       /* IHDR's interlace method: 0 none, 1 Adam7 (anything else is refused) */
 } maf_png_image_t;
 int maf_png_struct_sizes(int32_t* header_image);   /* sizeof of the two structs above (binding check) */
 /* inflated uint8 [inflated_bytes], rows uint8 [rows_bytes], out uint8 [out_bytes], status int32 [n_images]: device buffers, the first three

@@ -19,7 +19,9 @@
 //                         registers, 8 x 8-byte stores into the component plane (neighbouring threads write neighbouring 8 bytes of a row).
 //   jpeg_color_kernel     jdsample.c + jdcolor.c.  One thread per 4 output pixels of a row; the fancy upsampling is evaluated per pixel from
 //                         the chroma planes (neighbours clamped to the image's own ceil(w / 2) x ceil(h / 2) samples: the edge rules of
-//                         h2v*_fancy_upsample and the context rows of jdmainct.c), 12 bytes out as three 32-bit stores where aligned.
+//                         h2v*_fancy_upsample and the context rows of jdmainct.c), 12 bytes out as three 32-bit stores where aligned.  An image with an EXIF
+//                         orientation of 2 to 8 in its record is written through that permutation instead, pixel by pixel (the frame of
+//                         5 to 8 is [w][h][3]): the one place the baseline and the progressive chain both end.
 #include "maf_common.h"
 #include "jpeg_bits.h"
 
@@ -210,6 +212,22 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const maf_jpeg_image_t*
             px[3 * j + 2] = clamp_u8(yv + ((91881 * cr + 32768) >> 16));
         }
     }
+    if (im.orientation > 1) {
+        // EXIF orientation 2 to 8: the stored pixel (x, y) lands at (dx, dy) of a frame of W x H = w x h (2 to 4) or h x w (5 to 8); a
+        // permutation of the same 3 * w * h bytes, pixel by pixel (the stores of 5 to 8 run down a column)
+        const int ori = im.orientation;
+        const bool swap = ori >= 5;
+        const int W = swap ? h : w;
+        for (int j = 0; j < n; ++j) {
+            const int x = x0 + j;
+            const int fx = (ori == 2 || ori == 3 || ori == 7 || ori == 8) ? w - 1 - x : x;      // mirrored along the stored rows
+            const int fy = (ori == 3 || ori == 4 || ori == 6 || ori == 7) ? h - 1 - y : y;      // mirrored along the stored columns
+            const int dx = swap ? fy : fx, dy = swap ? fx : fy;
+            uint8_t* d = out + im.out_off + 3 * ((int64_t)dy * W + dx);
+            d[0] = px[3 * j]; d[1] = px[3 * j + 1]; d[2] = px[3 * j + 2];
+        }
+        return;
+    }
     const int64_t o = im.out_off + 3 * ((int64_t)y * w + x0);
     if (n == 4 && (o & 3) == 0) {
         uint32_t* d = reinterpret_cast<uint32_t*>(out + o);
@@ -259,6 +277,7 @@ extern "C" int maf_jpeg_decode(const void* blob_host, const void* blob_dev, int1
         MAF_REQUIRE(m.plane_off >= 0 && m.plane_off % 64 == 0 && m.plane_off + 64 * blocks <= hd.plane_bytes, "jpeg_decode: an image's planes lie outside the buffer");
         MAF_REQUIRE(m.out_off >= 0 && m.out_off % 16 == 0 && m.out_off + (int64_t)3 * m.w * m.h <= hd.out_bytes, "jpeg_decode: a frame lies outside the output buffer");
         MAF_REQUIRE(m.quant >= 0 && m.quant + 3 <= 3 * hd.n_images, "jpeg_decode: quantisation table index out of range");
+        MAF_REQUIRE(m.orientation >= 0 && m.orientation <= 8, "jpeg_decode: orientation is 0 (none) or an EXIF orientation 1 to 8");
         for (int c = 0; c < 3; ++c)
             MAF_REQUIRE((m.dc_tab[c] == 0 || m.dc_tab[c] == 1) && (m.ac_tab[c] == 0 || m.ac_tab[c] == 1), "jpeg_decode: Huffman table selector out of range");
         max_blocks = blocks > max_blocks ? blocks : max_blocks;

@@ -16,11 +16,13 @@
 //                         global memory as it is produced; a back-reference reads ONLY the ring, with a workgroup barrier between the lanes'
 //                         ring writes and any later read (one wave per workgroup, so the barrier costs a wait on the LDS counter).  Global memory is
 //                         never read back.
-//   png_unfilter_kernel   Filter types 0 to 4.  One wave per image walks bands of 64 rows: lane k works on row y0 + k, one pixel behind lane
+//   png_unfilter_kernel   Filter types 0 to 4.  One wave per image (per pass of an Adam7 image: each pass is a filter chain of its own, its first
+//                         row with zeros above it) walks bands of 64 rows: lane k works on row y0 + k, one pixel behind lane
 //                         k - 1, so the pixel above is what lane k - 1 produced one step ago (one shuffle) and the pixel above-left is the
 //                         `above` of the lane's own previous step.  Lane 0 reads the row above the band from the output of the band before (workgroup fence + barrier
 //                         between bands).  The next pixel's bytes are loaded one step ahead.
-//   png_convert_kernel    One thread per 4 pixels: strip 16 -> 8 (high byte), unpack 1 / 2 / 4 bit MSB first, gray x 255 / 85 / 17, palette from
+//   png_convert_kernel    One thread per 4 pixels: for an Adam7 image the gather (the pass from (x & 7, y & 7), the pixel's place in that pass's
+//                         sub-image), strip 16 -> 8 (high byte), unpack 1 / 2 / 4 bit MSB first, gray x 255 / 85 / 17, palette from
 //                         LDS, alpha dropped, BGR; 12 bytes out as three 32-bit stores.
 //
 // Bounded by construction (the inflate kernel reads bytes a file controls):
@@ -352,13 +354,39 @@ __device__ __forceinline__ uint64_t shfl_up1(uint64_t v) {
     return ((uint64_t)hi << 32) | lo;
 }
 
-__global__ __launch_bounds__(64) void png_unfilter_kernel(const maf_png_image_t* images, const uint8_t* inflated, uint8_t* rows, int32_t* status) {
-    const int lane = threadIdx.x;
-    const maf_png_image_t im = images[blockIdx.x];
-    const int rb = im.rowbytes, bpp = im.bpp, h = im.h;
+// Adam7 (PNG 1.2, 8.2): pass p holds the pixels (x0 + i * dx, y0 + j * dy) of the image as a sub-image of pw x ph pixels with rows of prb bytes,
+// filtered on its own; the passes follow each other in the stream, and a pass without pixels is absent (no filter bytes either).
+struct Adam7Pass {
+    int x0, y0, dx, dy, pw, ph, prb;
+};
+
+__host__ __device__ inline Adam7Pass adam7_pass(int w, int h, int bits, int p) {
+    constexpr int X0[7] = {0, 4, 0, 2, 0, 1, 0}, Y0[7] = {0, 0, 4, 0, 2, 0, 1}, DX[7] = {8, 8, 4, 4, 2, 2, 1}, DY[7] = {8, 8, 8, 4, 4, 2, 2};
+    Adam7Pass g;
+    g.x0 = X0[p]; g.y0 = Y0[p]; g.dx = DX[p]; g.dy = DY[p];
+    g.pw = w > g.x0 ? (w - g.x0 + g.dx - 1) / g.dx : 0;
+    g.ph = h > g.y0 ? (h - g.y0 + g.dy - 1) / g.dy : 0;
+    g.prb = (int)(((int64_t)g.pw * bits + 7) / 8);
+    return g;
+}
+
+// bytes of the passes in front of pass p: in the inflated stream (filter bytes included) and in the rows buffer (sub-images back to back)
+__host__ __device__ inline void adam7_offsets(int w, int h, int bits, int p, int64_t& inf, int64_t& rows) {
+    inf = rows = 0;
+    for (int q = 0; q < p; ++q) {
+        const Adam7Pass g = adam7_pass(w, h, bits, q);
+        if (g.pw == 0 || g.ph == 0) continue;
+        inf += (int64_t)g.ph * (1 + g.prb);
+        rows += (int64_t)g.ph * g.prb;
+    }
+}
+
+__host__ __device__ inline int png_channels(int ctype) { return ctype == 2 ? 3 : ctype == 4 ? 2 : ctype == 6 ? 4 : 1; }
+
+// One filter chain: h rows of 1 + rb bytes at src -> h rows of rb bytes at dst, the row above the first is zeros.  Called by the whole wave with
+// wave-uniform arguments (it holds workgroup barriers).  -> 1 in the lanes that met a filter type above 4.
+__device__ __forceinline__ int unfilter_chain(const uint8_t* src, uint8_t* dst, int rb, int bpp, int h, int lane) {
     const int npx = rb / bpp;                                  // rowbytes is a multiple of bpp (bpp is 1 below 8 bits)
-    const uint8_t* src = inflated + im.inf_off;
-    uint8_t* dst = rows + im.rows_off;
     int bad = 0;
     for (int y0 = 0; y0 < h; y0 += 64) {
         const int y = y0 + lane;
@@ -399,32 +427,70 @@ __global__ __launch_bounds__(64) void png_unfilter_kernel(const maf_png_image_t*
         __threadfence_block();                                 // the band's last row is read by lane 0 in the next band
         __syncthreads();
     }
+    return bad;
+}
+
+// grid (images, 1), or (images, 7) where the call holds an Adam7 file: workgroup (i, p) undoes pass p of image i, its own filter chain between
+// its own offsets; for a plain image workgroup (i, 0) undoes the whole image and the others leave at once, as does that of an absent pass.
+__global__ __launch_bounds__(64) void png_unfilter_kernel(const maf_png_image_t* images, const uint8_t* inflated, uint8_t* rows, int32_t* status) {
+    const int lane = threadIdx.x;
+    const maf_png_image_t im = images[blockIdx.x];
+    const uint8_t* src = inflated + im.inf_off;
+    uint8_t* dst = rows + im.rows_off;
+    int bad;
+    if (!im.interlace) {
+        if (blockIdx.y) return;
+        bad = unfilter_chain(src, dst, im.rowbytes, im.bpp, im.h, lane);
+    } else {
+        const int bits = png_channels(im.ctype) * im.depth;
+        const Adam7Pass g = adam7_pass(im.w, im.h, bits, (int)blockIdx.y);
+        if (g.pw == 0 || g.ph == 0) return;
+        int64_t inf, sub;
+        adam7_offsets(im.w, im.h, bits, (int)blockIdx.y, inf, sub);
+        bad = unfilter_chain(src + inf, dst + sub, g.prb, im.bpp, g.ph, lane);
+    }
     if (__any(bad) && lane == 0) atomicOr(&status[blockIdx.x], MAF_PNG_ST_BAD_FILTER);
 }
 
 __global__ __launch_bounds__(256) void png_convert_kernel(const maf_png_image_t* images, const uint32_t* palette, const uint8_t* rows, uint8_t* out,
                                                            int32_t* status) {
     __shared__ uint32_t lpal[256];
+    __shared__ int64_t sub_off[7];                             // Adam7: where each pass's sub-image begins inside the image's rows, and its row length
+    __shared__ int sub_rb[7];
     const maf_png_image_t im = images[blockIdx.y];
     const int tid = threadIdx.x;
     if ((int64_t)blockIdx.x * 1024 >= (int64_t)im.w * im.h) return;      // the grid is sized by the largest image of the call: a whole workgroup past this one leaves at once
     lpal[tid] = (im.ctype == 3 && tid < im.pal_n) ? palette[im.pal + tid] : 0u;
-    __syncthreads();
     const int w = im.w, depth = im.depth, ctype = im.ctype;
+    const int chans = png_channels(ctype);
+    const bool lace = im.interlace != 0;
+    if (lace && tid < 7) {
+        int64_t inf, sub;
+        adam7_offsets(w, im.h, chans * depth, tid, inf, sub);
+        sub_off[tid] = sub;
+        sub_rb[tid] = adam7_pass(w, im.h, chans * depth, tid).prb;
+    }
+    __syncthreads();
     const int64_t npix = (int64_t)w * im.h;
     const int64_t q = ((int64_t)blockIdx.x * 256 + tid) * 4;
     if (q >= npix) return;
     const int n = (int)min((int64_t)4, npix - q);
     const int step = depth == 16 ? 2 : 1;                      // bytes per sample; byte 0 of a big-endian pair is the high byte
-    const int chans = ctype == 2 ? 3 : ctype == 4 ? 2 : ctype == 6 ? 4 : 1;
     const uint8_t* base = rows + im.rows_off;
     uint8_t px[12];
     int bad = 0;
     for (int j = 0; j < 4; ++j) {
         px[3 * j] = px[3 * j + 1] = px[3 * j + 2] = 0;
         if (j >= n) continue;
-        const int y = (int)((q + j) / w), x = (int)((q + j) - (int64_t)y * w);
+        const int y = (int)((q + j) / w);
+        int x = (int)((q + j) - (int64_t)y * w);
         const uint8_t* row = base + (int64_t)y * im.rowbytes;
+        if (lace) {                                            // the gather: the pass from (x & 7, y & 7), then the pixel's place in that pass's sub-image
+            const int p = (y & 1) ? 6 : (x & 1) ? 5 : (y & 2) ? 4 : (x & 2) ? 3 : (y & 4) ? 2 : (x & 4) ? 1 : 0;
+            const Adam7Pass g = adam7_pass(w, im.h, 0, p);
+            row = base + sub_off[p] + (int64_t)((y - g.y0) / g.dy) * sub_rb[p];
+            x = (x - g.x0) / g.dx;
+        }
         if (ctype == 2 || ctype == 6) {
             const uint8_t* s = row + (int64_t)x * chans * step;
             px[3 * j] = s[2 * step];
@@ -486,21 +552,27 @@ extern "C" int maf_png_decode(const void* blob_host, const void* blob_dev, uint8
     const maf_png_image_t* ims = reinterpret_cast<const maf_png_image_t*>(hb + hd.images_off);
     const int64_t stream_data = hd.stream_bytes - MAF_PNG_STREAM_PAD;
     int64_t max_quads = 1;
+    bool any_interlaced = false;
     for (int i = 0; i < hd.n_images; ++i) {
         const maf_png_image_t& m = ims[i];
         MAF_REQUIRE(m.w > 0 && m.h > 0 && m.w <= 65535 && m.h <= 65535, "png_decode: bad image size");
         const bool d8 = m.depth == 8 || m.depth == 16, dlow = m.depth == 1 || m.depth == 2 || m.depth == 4;
         MAF_REQUIRE((m.ctype == 0 && (d8 || dlow)) || (m.ctype == 3 && (m.depth == 8 || dlow)) || ((m.ctype == 2 || m.ctype == 4 || m.ctype == 6) && d8),
                     "png_decode: colour type and bit depth do not go together");
-        const int chans = m.ctype == 2 ? 3 : m.ctype == 4 ? 2 : m.ctype == 6 ? 4 : 1;
+        const int chans = png_channels(m.ctype);
         const int64_t rowbits = (int64_t)m.w * chans * m.depth;
         MAF_REQUIRE(m.rowbytes == (rowbits + 7) / 8 && m.bpp == (chans * m.depth >= 8 ? chans * m.depth / 8 : 1), "png_decode: rowbytes or bpp does not match the image");
-        const int64_t size = (int64_t)m.h * (1 + (int64_t)m.rowbytes);
+        MAF_REQUIRE(m.interlace == 0 || m.interlace == 1, "png_decode: interlace is 0 (none) or 1 (Adam7)");
+        int64_t size = (int64_t)m.h * (1 + (int64_t)m.rowbytes), row_bytes = (int64_t)m.h * m.rowbytes;
+        if (m.interlace) {
+            adam7_offsets(m.w, m.h, chans * m.depth, 7, size, row_bytes);      // the sums over the non-empty passes
+            any_interlaced = true;
+        }
         MAF_REQUIRE(size < ((int64_t)1 << 31) && m.inflated_size == size, "png_decode: inflated size out of range");
         MAF_REQUIRE(m.stream_begin >= 0 && m.stream_begin <= m.stream_end && m.stream_end <= stream_data, "png_decode: an image's stream lies outside the stream section");
         MAF_REQUIRE(m.inf_off >= 0 && m.inf_off % 16 == 0 && m.inf_off <= hd.inflated_bytes && size <= hd.inflated_bytes - m.inf_off,
                     "png_decode: an image's scanlines lie outside the inflated buffer");
-        MAF_REQUIRE(m.rows_off >= 0 && m.rows_off % 16 == 0 && m.rows_off <= hd.rows_bytes && (int64_t)m.h * m.rowbytes <= hd.rows_bytes - m.rows_off,
+        MAF_REQUIRE(m.rows_off >= 0 && m.rows_off % 16 == 0 && m.rows_off <= hd.rows_bytes && row_bytes <= hd.rows_bytes - m.rows_off,
                     "png_decode: an image's rows lie outside the rows buffer");
         MAF_REQUIRE(m.out_off >= 0 && m.out_off % 16 == 0 && m.out_off <= hd.out_bytes && (int64_t)3 * m.w * m.h <= hd.out_bytes - m.out_off,
                     "png_decode: a frame lies outside the output buffer");
@@ -519,7 +591,7 @@ extern "C" int maf_png_decode(const void* blob_host, const void* blob_dev, uint8
         MAF_LAUNCH_CHECK("png_inflate");
     }
     if (stages & MAF_PNG_STAGE_UNFILTER) {
-        hipLaunchKernelGGL(png_unfilter_kernel, dim3(hd.n_images), dim3(64), 0, s, d_ims, inflated, rows, status);
+        hipLaunchKernelGGL(png_unfilter_kernel, dim3(hd.n_images, any_interlaced ? 7 : 1), dim3(64), 0, s, d_ims, inflated, rows, status);
         MAF_LAUNCH_CHECK("png_unfilter");
     }
     if (stages & MAF_PNG_STAGE_CONVERT) {

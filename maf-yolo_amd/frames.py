@@ -17,9 +17,10 @@ def kind(data):
     return None
 
 
-def decode(files, device=None, stream=None, check=True, progressive=False, ignore_orientation=False):
+def decode(files, device=None, stream=None, check=True, progressive=False, ignore_orientation=False, interlaced=False, apply_orientation=False):
     """Decode a list of JPEG and PNG files (bytes-like objects or paths, in any mix) on the device -> a list of uint8 [h_i, w_i, 3] BGR CUDA
-    tensors in input order, what cv2.imread returns for each file.  `progressive` and `ignore_orientation` go to jpeg.decode.  With
+    tensors in input order, what cv2.imread returns for each file.  `progressive`, `ignore_orientation` and `apply_orientation` go to jpeg.decode, `interlaced` to
+    png.decode (the last two only when set).  With
     check=False -> (frames, status int32 [len(files)] on the device: each file's status word of its own decoder, merged on `stream` behind the
     decoders' launches) without synchronising."""
     files = list(files)
@@ -40,9 +41,10 @@ def decode(files, device=None, stream=None, check=True, progressive=False, ignor
         sub = [datas[i] for i in idx]
         try:
             if k == "jpeg":
-                got = jpeg.decode(sub, device=device, stream=stream, ignore_orientation=ignore_orientation, check=check, progressive=progressive)
+                got = jpeg.decode(sub, device=device, stream=stream, ignore_orientation=ignore_orientation, check=check, progressive=progressive,
+                                  **(dict(apply_orientation=True) if apply_orientation else {}))
             else:
-                got = png.decode(sub, device=device, stream=stream, check=check)
+                got = png.decode(sub, device=device, stream=stream, check=check, **(dict(interlaced=True) if interlaced else {}))
         except MafError as e:
             # the decoders number the files of their own call: say which input each one is
             raise type(e)("%s [%s files of this call are inputs %s]" % (e, k, idx)) from None

@@ -11,7 +11,12 @@ The stage in front of letterbox.py / augment.py that the reference runs on the h
                       islow IDCT, fancy upsampling + YCbCr -> BGR), no host synchronisation unless check=True reads the status words.
 Supported: baseline sequential DCT (SOF0), 8 bit, Huffman, one interleaved scan, 1 component or 3 (Y 1x1, 2x1 or 2x2 with 1x1 chroma).
 The pixels follow libjpeg's JDCT_ISLOW + fancy upsampling + jdcolor.c tables as restated in tests/jpeg_ref.py.  cv2.imread also rotates by
-the EXIF orientation; this decoder does not, so such a file raises JpegUnsupported unless ignore_orientation=True.  No CPU fallback.
+the EXIF orientation; by default this decoder does not, so such a file raises JpegUnsupported unless ignore_orientation=True (the stored
+pixels).  No CPU fallback.
+Opt-in, apply_orientation=True on supported / decode: a file with an EXIF orientation of 2 to 8 decodes into the frame cv2.imread returns,
+[h, w, 3] for 2 to 4 and [w, h, 3] for 5 to 8; the orientation travels in the image table and the colour kernel's final store goes through
+the permutation (rules restated in tests/jpeg_orientation_ref.py), for baseline and progressive files alike.  A tag value outside 1 to 8
+stays refused; together with ignore_orientation it is a MafError.  Without the flag nothing changes.
 Opt-in, progressive=True on parse / supported / decode: progressive DCT (SOF2, 8 bit, Huffman) with the same components and samplings, every
 scan of the file walked and validated as jdphuff.c start_pass_phuff_decoder does (JpegInfo.scans: one JpegScan per SOS with the Huffman
 tables and the restart interval in force there); csrc/jpeg_progressive.hip decodes scan k of every file of the call in launch k, the IDCT
@@ -405,11 +410,11 @@ def parse(data, progressive=False):
     return JpegInfo(w, h, 8, tuple(comps), qt, huff, restart, (p, end), orientation, adobe)
 
 
-def supported(data, progressive=False):
+def supported(data, progressive=False, apply_orientation=False):
     """True where decode() takes this file: a baseline JPEG (with progressive=True also a progressive one) of the supported set without an
-    EXIF rotation."""
+    EXIF rotation; with apply_orientation=True also one with an EXIF orientation of 2 to 8."""
     try:
-        return parse(data, progressive).orientation in (None, 1)
+        return parse(data, progressive).orientation in ((None,) + tuple(range(1, 9)) if apply_orientation else (None, 1))
     except MafError:
         return False
 
@@ -424,7 +429,7 @@ WAVE_SLOTS = 2048             # 256 CUs x 8: while the chip has free slots a wav
 
 IMAGE_DT = np.dtype([("coef_off", "<i8"), ("plane_off", "<i8"), ("out_off", "<i8"), ("w", "<i4"), ("h", "<i4"), ("ncomp", "<i4"), ("hs", "<i4"),
                      ("vs", "<i4"), ("mcux", "<i4"), ("mcuy", "<i4"), ("quant", "<i4"), ("dc_tab", "<i4", 3), ("ac_tab", "<i4", 3),
-                     ("reserved", "<i4", 2)])              # maf_jpeg_image_t
+                     ("orientation", "<i4"), ("reserved", "<i4")])   # maf_jpeg_image_t
 LANE_DT = np.dtype([("begin", "<i8"), ("end", "<i8"), ("image", "<i4"), ("first_mcu", "<i4"), ("n_mcu", "<i4"), ("tabset", "<i4")])   # maf_jpeg_lane_t
 HEADER_DT = np.dtype([("n_images", "<i4"), ("n_lanes", "<i4"), ("n_tabsets", "<i4"), ("group", "<i4"), ("images_off", "<i8"), ("lanes_off", "<i8"),
                       ("huff_off", "<i8"), ("quant_off", "<i8"), ("scan_off", "<i8"), ("scan_bytes", "<i8"), ("total_bytes", "<i8"),
@@ -509,11 +514,12 @@ def _group_of(n_lanes):
     return group
 
 
-def build_blob(datas, infos):
+def build_blob(datas, infos, apply_orientation=False):
     """Everything the device needs for one call, in one byte array: header | image table | lane table | Huffman table sets | quantisation
     tables | with progressive files: scan table | scan lanes | round starts | the scans' bytes + SCAN_PAD zeros.
     -> (header record, image table, lane table, Huffman table sets, quantisation tables, each file's offset in the scan bytes,
-    (scan table, scan lanes, round starts) or None)."""
+    (scan table, scan lanes, round starts) or None).  apply_orientation: the image table carries each file's EXIF orientation (else 0: the
+    stored grid)."""
     B = len(infos)
     images = np.zeros(B, IMAGE_DT)
     quant = np.zeros((B, 3, 64), np.uint16)
@@ -535,6 +541,8 @@ def build_blob(datas, infos):
         im = images[i]
         im["coef_off"], im["plane_off"], im["out_off"] = coef, plane, outb
         im["w"], im["h"], im["ncomp"], im["hs"], im["vs"], im["mcux"], im["mcuy"], im["quant"] = info.width, info.height, nc, hs, vs, mcux, mcuy, 3 * i
+        if apply_orientation and info.orientation is not None:
+            im["orientation"] = info.orientation
         for c, comp in enumerate(info.components):
             quant[i, c] = info.qtables[comp.tq]
             im["dc_tab"][c], im["ac_tab"][c] = comp.td, comp.ta
@@ -617,28 +625,42 @@ _library = partial(staging.checked_library, "jpeg", (("maf_jpeg_struct_sizes", 3
 status_text = partial(staging.status_text, _STATUS_TEXT)
 
 
-def decode(files, device=None, stream=None, ignore_orientation=False, check=True, stages=STAGE_ALL, taps=None, progressive=False):
+def decode(files, device=None, stream=None, ignore_orientation=False, check=True, stages=STAGE_ALL, taps=None, progressive=False,
+           apply_orientation=False):
     """Decode a list of baseline JPEG files (bytes-like objects or paths; mixed sizes and samplings welcome) on the device; with
     progressive=True the list may also hold progressive files (scan k of every file of the call is one launch: jpeg_prog_entropy_kernel).
     -> a list of uint8 [h_i, w_i, 3] BGR CUDA tensors (views of one allocation), what cv2.imread returns for each file; they go into
     letterbox / eval_batch / detect_frames / train_batch as they are.  With check=True (the default) the per-image status words are read
     once after the launches (the call's one synchronisation) and a fault raises MafError naming the file; check=False returns
     (frames, status int32 [B]) without synchronising.  `stream`: a torch.cuda.Stream to work on (default: the current one).
-    `taps`: a dict that receives the intermediate buffers (coefficients, planes, the image table; "progressive": the scan table, the scan
-    lanes and the round starts, or None) — tests and the probe."""
+    apply_orientation=True: a file with an EXIF orientation of 2 to 8 decodes into the frame cv2.imread returns, [h, w, 3] for 2 to 4 and
+    [w, h, 3] for 5 to 8 (the colour kernel's final store goes through the permutation: no further launch or buffer); a tag value outside
+    1 to 8 stays refused.  Not together with ignore_orientation.
+    `taps`: a dict that receives the intermediate buffers (coefficients, planes, the image table with h and w as the frames have them;
+    "progressive": the scan table, the scan lanes and the round starts, or None) — tests and the probe."""
     extra = {}
+    if apply_orientation and ignore_orientation:
+        raise MafError("jpeg.decode: apply_orientation and ignore_orientation exclude each other (rotate the frame, or take the stored pixels)")
 
     def parse_one(d):
         info = parse(d, progressive)
-        if info.orientation not in (None, 1) and not ignore_orientation:
+        if apply_orientation:
+            if info.orientation is not None and not 1 <= info.orientation <= 8:
+                raise JpegUnsupported("jpeg: EXIF orientation %d is not one of 1 to 8" % info.orientation)
+        elif info.orientation not in (None, 1) and not ignore_orientation:
             raise JpegUnsupported("jpeg: EXIF orientation %d — cv2.imread would rotate the frame, this decoder does not "
                                   "(pass ignore_orientation=True to take the stored pixels)" % info.orientation)
         return info
 
     def build(datas, infos):
-        hdr, images, lanes, huff, quant, scan_at, prog = build_blob(datas, infos)
+        hdr, images, lanes, huff, quant, scan_at, prog = build_blob(datas, infos, apply_orientation)
         extra["progressive"] = prog
-        return hdr, images, lambda host: fill_blob(host, hdr, images, lanes, huff, quant, datas, infos, scan_at, prog)
+        shown = images
+        if (images["orientation"] >= 5).any():                   # the frames of orientations 5 to 8 are [w, h, 3]: the views' table, not the blob's
+            shown = images.copy()
+            turned = shown["orientation"] >= 5
+            shown["h"][turned], shown["w"][turned] = images["w"][turned], images["h"][turned]
+        return hdr, shown, lambda host: fill_blob(host, hdr, images, lanes, huff, quant, datas, infos, scan_at, prog)
 
     def launch(L, s, blob, hdr, out, status):
         import torch

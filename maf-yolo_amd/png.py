@@ -3,7 +3,7 @@
 The stage in front of letterbox.py / augment.py that the reference runs on the host, one file at a time, through cv2.imread, for the png
 entries of IMG_FORMATS (yolov6/data/datasets.py load_image, LoadData of yolov6/core/inferer.py):
   * parse(data)       host only: walks the chunks of one file -> PngInfo (size, bit depth, colour type, palette, the IDAT byte ranges, the
-                      expected inflated size h * (1 + rowbytes)).  The CRC-32 of every critical chunk is checked (zlib.crc32).
+                      expected inflated size h * (1 + rowbytes), for an Adam7 file the sum over its passes).  The CRC-32 of every critical chunk is checked (zlib.crc32).
                       PngUnsupported names everything outside the supported set, MafError a corrupt file;
   * supported(data)   True where decode() takes the file (a caller routes the others to the host decoder);
   * decode(files)     a list of bytes-like objects or paths -> a list of uint8 [h_i, w_i, 3] BGR CUDA tensors: ONE pinned staging buffer, ONE
@@ -17,8 +17,11 @@ PNG is lossless, so the samples of a file are the same for every conforming deco
     palette 1 / 2 / 4 / 8    PLTE lookup (png_set_palette_to_rgb), BGR; tRNS ignored
     any 16-bit type          the HIGH byte of every sample (png_set_strip_16), then as the 8-bit type
 tRNS only makes an alpha that is then dropped, so it is ignored everywhere; gAMA, sRGB, iCCP, pHYs, text and every other ancillary chunk are
-skipped (their CRC is not checked).  The Adler-32 at the end of the zlib stream is not verified.  Refused (PngUnsupported): Adam7
-interlacing, a compression or filter method other than 0, a zlib header with a preset dictionary or a method other than deflate, APNG (an
+skipped (their CRC is not checked), eXIf among them: no PNG file is rotated.  The Adler-32 at the end of the zlib stream is not verified.
+Opt-in, interlaced=True on parse / supported / decode: Adam7 files (interlace method 1), in any mix with plain ones, from the same three
+launches: every pass is a filter chain of its own for the unfilter kernel, and the convert kernel gathers each pixel from its pass (rules
+restated in tests/png_adam7_ref.py).  Without the flag nothing changes.  Refused (PngUnsupported): Adam7 interlacing without the flag, any
+other interlace method, a compression or filter method other than 0, a zlib header with a preset dictionary or a method other than deflate, APNG (an
 acTL chunk), an unknown critical chunk, a side above 65535 or 2 GiB of scanlines.  A palette index past PLTE is found on the device and
 reported as a status bit.  No CPU fallback.
 """
@@ -39,13 +42,15 @@ class PngUnsupported(MafError):
 
 
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
-PngInfo = namedtuple("PngInfo", "width height bit_depth color_type palette idat inflated_size rowbytes channels bpp")
+PngInfo = namedtuple("PngInfo", "width height bit_depth color_type palette idat inflated_size rowbytes channels bpp interlace", defaults=(0,))
 # palette: uint8 [n, 3] RGB (colour type 3) or None; idat: ((first byte, one past the last byte), ...) of the IDAT payloads in file order (their
-# concatenation is the zlib stream); inflated_size = height * (1 + rowbytes); bpp: the filters' byte distance max(1, channels * bit_depth / 8)
+# concatenation is the zlib stream); inflated_size = height * (1 + rowbytes), for an Adam7 file the sum of ph * (1 + prb) over its non-empty
+# passes; bpp: the filters' byte distance max(1, channels * bit_depth / 8); interlace: IHDR's interlace method, 0 or 1 (Adam7)
 
 CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}
 DEPTHS = {0: (1, 2, 4, 8, 16), 2: (8, 16), 3: (1, 2, 4, 8), 4: (8, 16), 6: (8, 16)}
 MAX_SIDE = 65535              # the limit jpeg.py has from its 16-bit fields
+ADAM7 = ((0, 0, 8, 8), (4, 0, 8, 8), (0, 4, 4, 8), (2, 0, 4, 4), (0, 2, 2, 4), (1, 0, 2, 2), (0, 1, 1, 2))    # per pass: x0, y0, dx, dy (PNG 1.2, 8.2)
 
 (STATUS_INPUT_EXHAUSTED, STATUS_BAD_BLOCK_TYPE, STATUS_BAD_STORED_LEN, STATUS_BAD_CODE_LENGTHS, STATUS_NO_CODE, STATUS_DISTANCE_TOO_FAR,
  STATUS_TOO_MANY_BYTES, STATUS_TOO_FEW_BYTES, STATUS_BAD_FILTER, STATUS_BAD_PALETTE_INDEX) = (1 << i for i in range(10))   # MAF_PNG_ST_*
@@ -56,8 +61,31 @@ _STATUS_TEXT = ((STATUS_INPUT_EXHAUSTED, "a deflate stream that ends early"), (S
                 (STATUS_BAD_FILTER, "a filter type above 4"), (STATUS_BAD_PALETTE_INDEX, "a palette index past PLTE"))
 
 
-def parse(data):
-    """Walk the chunks of one PNG file (bytes-like or a path) -> PngInfo.  Host only."""
+def adam7_passes(w, h, bits):
+    """The seven passes of a w x h Adam7 image with `bits` bits per pixel -> [(pw, ph, prb)]: pixels per row, rows, bytes per row of the
+    pass's sub-image.  A pass with pw == 0 or ph == 0 is absent from the stream (no filter bytes either)."""
+    out = []
+    for x0, y0, dx, dy in ADAM7:
+        pw, ph = max(0, -(-(w - x0) // dx)), max(0, -(-(h - y0) // dy))
+        out.append((pw, ph, (pw * bits + 7) // 8))
+    return out
+
+
+def adam7_sizes(w, h, bits):
+    """(the inflated size, the bytes of the unfiltered sub-images back to back) of an Adam7 image."""
+    live = [(ph, prb) for pw, ph, prb in adam7_passes(w, h, bits) if pw and ph]
+    return sum(ph * (1 + prb) for ph, prb in live), sum(ph * prb for ph, prb in live)
+
+
+def rows_size(info):
+    """Bytes of the unfiltered rows of a parsed file: h * rowbytes, or the Adam7 sub-images back to back (more than that below 8 bits)."""
+    if info.interlace:
+        return adam7_sizes(info.width, info.height, info.channels * info.bit_depth)[1]
+    return info.height * info.rowbytes
+
+
+def parse(data, interlaced=False):
+    """Walk the chunks of one PNG file (bytes-like or a path) -> PngInfo.  Host only.  interlaced=True also takes Adam7 files (interlace method 1)."""
     d = file_bytes(data)
     n = len(d)
     if d[:8] != SIGNATURE:
@@ -111,7 +139,7 @@ def parse(data):
         raise MafError("png: zero width or height")
     if comp != 0 or filt != 0:
         raise PngUnsupported("png: compression method %d / filter method %d is not supported (0 / 0 only)" % (comp, filt))
-    if lace != 0:
+    if lace != 0 and not (interlaced and lace == 1):
         raise PngUnsupported("png: Adam7 interlacing is not supported" if lace == 1 else "png: interlace method %d is not supported" % lace)
     if w > MAX_SIDE or h > MAX_SIDE:
         raise PngUnsupported("png: %d x %d is beyond the %d x %d limit" % (w, h, MAX_SIDE, MAX_SIDE))
@@ -137,16 +165,16 @@ def parse(data):
         raise MafError("png: a corrupt zlib header")
     ch = CHANNELS[ctype]
     rowbytes = (w * ch * depth + 7) // 8
-    size = h * (1 + rowbytes)
+    size = adam7_sizes(w, h, ch * depth)[0] if lace else h * (1 + rowbytes)
     if size >= 2 ** 31:
         raise PngUnsupported("png: %d x %d at %d bits per pixel is beyond the 2 GiB of scanlines decode() takes" % (w, h, ch * depth))
-    return PngInfo(w, h, depth, ctype, palette if ctype == 3 else None, tuple(idat), size, rowbytes, ch, max(1, ch * depth // 8))
+    return PngInfo(w, h, depth, ctype, palette if ctype == 3 else None, tuple(idat), size, rowbytes, ch, max(1, ch * depth // 8), lace)
 
 
-def supported(data):
-    """True where decode() takes this file."""
+def supported(data, interlaced=False):
+    """True where decode() takes this file (interlaced=True: where decode(..., interlaced=True) does)."""
     try:
-        parse(data)
+        parse(data, interlaced)
         return True
     except MafError:
         return False
@@ -156,7 +184,7 @@ def supported(data):
 
 IMAGE_DT = np.dtype([("stream_begin", "<i8"), ("stream_end", "<i8"), ("inf_off", "<i8"), ("rows_off", "<i8"), ("out_off", "<i8"), ("w", "<i4"),
                      ("h", "<i4"), ("depth", "<i4"), ("ctype", "<i4"), ("rowbytes", "<i4"), ("bpp", "<i4"), ("inflated_size", "<i4"), ("pal", "<i4"),
-                     ("pal_n", "<i4"), ("reserved", "<i4")])   # maf_png_image_t
+                     ("pal_n", "<i4"), ("interlace", "<i4")])   # maf_png_image_t
 HEADER_DT = np.dtype([("n_images", "<i4"), ("n_palette", "<i4"), ("images_off", "<i8"), ("palette_off", "<i8"), ("stream_off", "<i8"),
                       ("stream_bytes", "<i8"), ("total_bytes", "<i8"), ("inflated_bytes", "<i8"), ("rows_bytes", "<i8"), ("out_bytes", "<i8")])   # maf_png_header_t
 STREAM_PAD = 64               # zero bytes the host appends to the streams (the bit reader's clamp lands in them)
@@ -175,7 +203,7 @@ def build_blob(infos):
         im["stream_begin"], im["stream_end"] = at + 2, at + zbytes         # behind the 2-byte zlib header
         im["inf_off"], im["rows_off"], im["out_off"] = inf, rows, outb
         im["w"], im["h"], im["depth"], im["ctype"] = info.width, info.height, info.bit_depth, info.color_type
-        im["rowbytes"], im["bpp"], im["inflated_size"] = info.rowbytes, info.bpp, info.inflated_size
+        im["rowbytes"], im["bpp"], im["inflated_size"], im["interlace"] = info.rowbytes, info.bpp, info.inflated_size, info.interlace
         if info.palette is not None:
             e = np.zeros((len(info.palette), 4), np.uint8)
             e[:, :3] = info.palette[:, ::-1]
@@ -184,7 +212,7 @@ def build_blob(infos):
             npal += len(e)
         at += zbytes
         inf += _align(info.inflated_size)
-        rows += _align(info.height * info.rowbytes)
+        rows += _align(rows_size(info))
         outb += _align(3 * info.width * info.height)
     palette = np.concatenate(pals) if pals else np.zeros((0, 4), np.uint8)
     hdr, off = staging.blob_layout(HEADER_DT, (("images_off", images), ("palette_off", palette)))
@@ -213,8 +241,10 @@ _library = partial(staging.checked_library, "png", (("maf_png_struct_sizes", 2),
 status_text = partial(staging.status_text, _STATUS_TEXT)
 
 
-def decode(files, device=None, stream=None, check=True, stages=STAGE_ALL, taps=None):
-    """Decode a list of PNG files (bytes-like objects or paths; mixed sizes, colour types and bit depths welcome) on the device.
+def decode(files, device=None, stream=None, check=True, stages=STAGE_ALL, taps=None, interlaced=False):
+    """Decode a list of PNG files (bytes-like objects or paths; mixed sizes, colour types and bit depths welcome) on the device; with
+    interlaced=True the list may also hold Adam7 files, in any mix with plain ones (the same three launches: the unfilter kernel undoes each
+    pass as a filter chain of its own, the convert kernel gathers every pixel from its pass).
     -> a list of uint8 [h_i, w_i, 3] BGR CUDA tensors (views of one allocation), what cv2.imread returns for each file; they go into
     letterbox / eval_batch / detect_frames / train_batch as they are.  With check=True (the default) the per-image status words are read
     once after the launches (the call's one synchronisation) and a fault raises MafError naming the file and its status bits; check=False
@@ -234,4 +264,4 @@ def decode(files, device=None, stream=None, check=True, stages=STAGE_ALL, taps=N
                                    int(stages), s.stream.cuda_stream))
         return dict(inflated=inflated, rows=rows)
 
-    return staging.decode_files("png.decode", files, parse, build, _library, launch, _STATUS_TEXT, True, device, stream, check, taps)
+    return staging.decode_files("png.decode", files, partial(parse, interlaced=True) if interlaced else parse, build, _library, launch, _STATUS_TEXT, True, device, stream, check, taps)

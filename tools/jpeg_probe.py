@@ -1,6 +1,6 @@
 """Measurements of the JPEG decoder (csrc/jpeg_decode.hip, maf-yolo_amd/jpeg.py) on the GPU; prints ONE JSON line.
 
-    python tools/jpeg_probe.py [--iters N] [--batches 32,256,1024] [--progressive]
+    python tools/jpeg_probe.py [--iters N] [--batches 32,256,1024] [--progressive] [--orientation]
 
 The file is the 480 x 640, 4:2:0, quality 90 case of tests/golden/jpeg_cases.npz replicated to B files per call.  Per B:
 * images/s of decode(files, check=False) end to end (host parse + staging + copy + the three kernels), wall clock over `iters` calls with
@@ -13,6 +13,8 @@ Where Pillow is importable, the single-thread Pillow decode time of the same fil
 progressive=True; per B additionally the launch count of a call (memsets aside: one entropy launch per scan round + IDCT + colour), the entropy
 stage as a whole (the coefficient memset and all rounds, which follow each other on the stream) and its mean per round, and under "baseline"
 the figures of the baseline file at the same B, measured in the same run.
+--orientation: instead, the per-stage device times of the baseline file with the image table's orientation set to 1 and to 2 ... 8 (the scan
+bytes are the same: only the colour kernel's final store differs), decoded frames checked against the permuted orientation-1 frame.
 """
 import argparse
 import io
@@ -32,10 +34,12 @@ from maf_yolo_amd import jpeg as J, lib  # noqa: E402
 DEV = torch.device("cuda:0")
 
 
-def stage_times(files, iters, progressive=False):
-    """Event time of each stage alone, on buffers a full decode has filled."""
+def stage_times(files, iters, progressive=False, orientation=0, frames=None):
+    """Event time of each stage alone, on buffers a full decode has filled.  orientation: written into every image's record; frames: a list
+    that receives the output buffer and the image table."""
     infos = [J.parse(f, progressive) for f in files]
     hdr, images, lanes, huff, quant, scan_at, prog = J.build_blob(files, infos)
+    images["orientation"] = orientation
     stage = torch.empty(int(hdr["total_bytes"]), dtype=torch.uint8, pin_memory=True)
     host = stage.numpy()
     J.fill_blob(host, hdr, images, lanes, huff, quant, files, infos, scan_at, prog)
@@ -60,6 +64,8 @@ def stage_times(files, iters, progressive=False):
             torch.cuda.synchronize()
             ts.append(e0.elapsed_time(e1) * 1e3)
         res[name + "_us"] = round(statistics.median(ts), 1)
+    if frames is not None:
+        frames += [out, images]
     res["bytes"] = dict(h2d=int(hdr["total_bytes"]), coef_write_read=4 * int(hdr["coef_elems"]), planes_write_read=2 * int(hdr["plane_bytes"]),
                         frames=int(hdr["out_bytes"]), lanes=int((lanes["image"] >= 0).sum()))
     if prog is not None:
@@ -111,10 +117,30 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--batches", default="32,256,1024")
     ap.add_argument("--progressive", action="store_true", help="measure the progressive encoding of the same picture (and the baseline one beside it)")
+    ap.add_argument("--orientation", action="store_true", help="measure the colour stage with the EXIF orientation 1 ... 8 in the image table")
     args = ap.parse_args()
     data = np.load(os.path.join(ROOT, "tests", "golden", "jpeg_cases.npz"))["large_file"].tobytes()
     res = {"metric": "jpeg_probe", "file": "480x640 4:2:0 q90, %d bytes" % len(data), "cases": {}}
     res["pillow_single_thread_ms"] = pillow_ms(data)
+    if args.orientation:
+        res["metric"] = "jpeg_probe_orientation"
+        for B in [int(b) for b in args.batches.split(",")]:
+            c, upright = {}, None
+            for o in range(1, 9):
+                got = []
+                t = stage_times([data] * B, max(3, args.iters), orientation=o, frames=got)
+                out, images = got
+                h, w = int(images[0]["h"]), int(images[0]["w"])
+                first = out[:3 * h * w].view(*((w, h, 3) if o >= 5 else (h, w, 3))).cpu()
+                if o == 1:
+                    upright = first
+                flip = {2: lambda f: f.flip(1), 3: lambda f: f.flip(0, 1), 4: lambda f: f.flip(0), 5: lambda f: f.transpose(0, 1),
+                        6: lambda f: f.flip(0).transpose(0, 1), 7: lambda f: f.flip(0, 1).transpose(0, 1), 8: lambda f: f.flip(1).transpose(0, 1)}
+                assert o == 1 or torch.equal(first, flip[o](upright)), o
+                c[str(o)] = {k: t[k] for k in ("entropy_us", "idct_us", "color_us", "all_us")}
+            res["cases"][str(B)] = c
+        print(json.dumps(res))
+        return
     if args.progressive:
         pdata = np.load(os.path.join(ROOT, "tests", "golden", "jpeg_progressive_cases.npz"))["large_file"].tobytes()
         res["metric"] = "jpeg_probe_progressive"

@@ -1,7 +1,7 @@
 """Measurements of the PNG decoder (csrc/png_decode.hip, maf-yolo_amd/png.py) on the GPU; prints ONE JSON line and writes it to
 profiles/png_probe.json.
 
-    python tools/png_probe.py [--iters N] [--batches 32,256,1024]
+    python tools/png_probe.py [--iters N] [--batches 32,256,1024] [--interlaced]
 
 The file is the 480 x 640 picture of tests/golden/jpeg_cases.npz (its large case, decoded by Pillow) re-encoded by Pillow as an RGB PNG and
 replicated to B files per call.  Per B:
@@ -12,6 +12,9 @@ replicated to B files per call.  Per B:
   file of the call has a wave of its own (B = 32: the per-stream rate, to be read against jpeg_entropy_kernel's per-file time in DESIGN.md);
 * bytes moved per call.
 The single-thread Pillow decode time of the same file on the same host stands beside them.
+--interlaced: instead, the same 480 x 640 pixels assembled by hand (tests/png_ref.py, tests/png_adam7_ref.py: filter types cycled, zlib level 6) as a
+plain and as an Adam7 file; per B the per-stage device times of both (decoded with interlaced=True) and of a call that alternates them; one JSON
+line, written to profiles/png_probe_interlaced.json.
 """
 import argparse
 import io
@@ -41,9 +44,9 @@ def host_ms(files):
     return round((time.perf_counter() - t0) * 1e3, 2)
 
 
-def stage_times(files, iters):
+def stage_times(files, iters, interlaced=False):
     """Event time of each stage alone, on buffers a full decode has filled."""
-    infos = [P.parse(f) for f in files]
+    infos = [P.parse(f, interlaced) for f in files]
     hdr, images, palette = P.build_blob(infos)
     stage = torch.empty(int(hdr["total_bytes"]), dtype=torch.uint8, pin_memory=True)
     host = stage.numpy()
@@ -105,12 +108,41 @@ def measure(data, B, iters):
     return c
 
 
+def interlaced_leg(jpg, batches, iters):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import png_adam7_ref as A
+    import png_ref as R
+    rgb = np.asarray(Image.open(io.BytesIO(jpg)).convert("RGB"))
+    rows = np.ascontiguousarray(rgb).reshape(rgb.shape[0], -1)
+    plain = R.encode(rows, rgb.shape[1], 8, 2, level=6)[0]
+    laced = A.encode(rows, rgb.shape[1], 8, 2, level=6)[0]
+    want = torch.from_numpy(np.ascontiguousarray(rgb[:, :, ::-1]))
+    got = P.decode([plain, laced], device=DEV, interlaced=True)
+    assert torch.equal(got[0].cpu(), want) and torch.equal(got[1].cpu(), want)
+    res = {"metric": "png_probe_interlaced", "file": "%dx%d RGB 8, filter types cycled, zlib level 6" % rgb.shape[:2],
+           "plain_bytes": len(plain), "interlaced_bytes": len(laced), "plain_inflated": P.parse(plain).inflated_size,
+           "interlaced_inflated": P.parse(laced, True).inflated_size, "cases": {}}
+    for B in batches:
+        res["cases"][str(B)] = dict(plain=stage_times([plain] * B, iters, True), interlaced=stage_times([laced] * B, iters, True),
+                                    alternating=stage_times([plain, laced] * (B // 2), iters, True))
+        torch.cuda.empty_cache()
+    return res, "png_probe_interlaced.json"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--batches", default="32,256,1024")
+    ap.add_argument("--interlaced", action="store_true", help="measure the same pixels as a plain and as an Adam7 file, stage by stage")
     args = ap.parse_args()
     jpg = np.load(os.path.join(ROOT, "tests", "golden", "jpeg_cases.npz"))["large_file"].tobytes()
+    if args.interlaced:
+        res, name = interlaced_leg(jpg, [int(b) for b in args.batches.split(",")], max(3, args.iters))
+        line = json.dumps(res)
+        with open(os.path.join(ROOT, "profiles", name), "w") as f:
+            f.write(line + "\n")
+        print(line)
+        return
     buf = io.BytesIO()
     Image.open(io.BytesIO(jpg)).convert("RGB").save(buf, "PNG")
     data = buf.getvalue()
