@@ -1,5 +1,5 @@
 """fp64 restatement of every op kind of an fp16 launch plan, from the op's MafOp, its plan record (engine.Plan._ops[i], whose `raw` holds the fp32 weights
-the packer consumed) and snapshots of the op's source slices: the 1x1 conv over concatenated sources (SRC_DIRECT / SRC_UP2 / SRC_POOL2, fp16 or fp32
+the packer consumed) and snapshots of the op's source slices: the 1x1 conv over concatenated sources (SRC_DIRECT / SRC_UP2 / SRC_POOL2 / SRC_SUB2, fp16 or fp32
 output), the 3x3 stride-2 conv (twin, one-launch MPRep `pool1`), the depth-wise conv (one or two filters per input channel), the stem pair (u8 / f16 / f32
 image, optional third conv, optional split second output), the fused bottleneck (with and without the block's closing conv), conv1 + depth-wise, SPPF's
 three max-pools and the head tail (decoded through oracle.maf_oracle.decode).
@@ -77,6 +77,8 @@ def _src(x, mode, H, W):
     if mode == lib.SRC_POOL2:
         B, _, _, C = x.shape
         return x[:, :2 * H, :2 * W].reshape(B, H, 2, W, 2, C).amax((2, 4))
+    if mode == lib.SRC_SUB2:                                   # pixel (2y, 2x) of a 2H x 2W source: a 1x1 conv with stride 2
+        return x[:, :2 * H:2, :2 * W:2]
     raise ValueError(mode)
 
 
@@ -145,6 +147,14 @@ def _stem_input(x, in_dtype):
     return x.permute(0, 2, 3, 1).double()
 
 
+def _stem1_input(x, in_dtype):
+    """The image as the single stem conv (csrc/stem.hip) reads it: [B, 3, H, W] -> NHWC in fp32, never rounded to fp16 (u8: x * (1 / 255) in fp32), float64."""
+    x = x.float()
+    if in_dtype == lib.U8:
+        x = x * torch.tensor(1.0 / 255.0, dtype=torch.float32)
+    return x.permute(0, 2, 3, 1).double()
+
+
 def _out(ref, S, k, f32=False):
     return ref, bound(ref, S, f32, k), S
 
@@ -154,23 +164,27 @@ def reference(op, rec, srcs, dev, twin_src=None, image=None):
     image: the stem's [B, 3, Hin, Win] input tensor."""
     kind = op.kind
     raw = [t.to(dev) for t in rec.get("raw", ()) if t is not None and torch.is_tensor(t)]
+    f32 = op.dtype == lib.F32                                  # an fp32 launch (the edge suite; the plans are fp16) stores fp32: its ulp
+    if kind == lib.OP_STEM:                                    # fp32 weights and fp32 arithmetic on the image as loaded: 27 products
+        w, b = raw[:2]
+        return {"out": _out(*_conv3x3s2(_stem1_input(image, op.in_dtype), w.double(), b.double(), lib.ACT_RELU, op.H, op.W), K_CONV, f32)}
     if kind == lib.OP_CONV1X1:
         w, b = raw[:2]
         x = torch.cat([_src(s, op.src[k].mode, op.H, op.W) for k, s in enumerate(srcs)], -1)
-        return {"out": _out(*_mm(x, _w16(w.reshape(w.shape[0], -1)), b.double(), op.act), K_CONV, bool(op.out_f32))}
+        return {"out": _out(*_mm(x, _w16(w.reshape(w.shape[0], -1)), b.double(), op.act), K_CONV, bool(op.out_f32) or f32)}
     if kind == lib.OP_CONV3X3S2:
         w, b = raw[:2]
-        out = {"out": _out(*_conv3x3s2(srcs[0].double(), _w16(w), b.double(), op.act, op.H, op.W), K_CONV)}
+        out = {"out": _out(*_conv3x3s2(srcs[0].double(), _w16(w), b.double(), op.act, op.H, op.W), K_CONV, f32)}
         if rec.get("pool1"):
             w1, b1 = (t.to(dev) for t in rec["pool1"])
             out["pool"] = _out(*_mm(_src(srcs[0], lib.SRC_POOL2, op.H, op.W), _w16(w1.reshape(w1.shape[0], -1)), b1.double(), lib.ACT_SILU), K_CONV)
         if rec.get("twin"):
             w2, b2 = (t.to(dev) for t in rec["twin"]["raw"])
-            out["twin"] = _out(*_conv3x3s2(twin_src.double(), _w16(w2), b2.double(), op.act, op.H, op.W), K_CONV)
+            out["twin"] = _out(*_conv3x3s2(twin_src.double(), _w16(w2), b2.double(), op.act, op.H, op.W), K_CONV, f32)
         return out
     if kind == lib.OP_DWCONV:
         w, b = raw
-        return {"out": _out(*_dw(srcs[0].double(), _w16(w), b.double(), op.act, op.Cout), K_CONV)}
+        return {"out": _out(*_dw(srcs[0].double(), _w16(w), b.double(), op.act, op.Cout), K_CONV, f32)}
     if kind == lib.OP_SPPF_POOL:
         x = srcs[0].double().permute(0, 3, 1, 2)
         ys = []
