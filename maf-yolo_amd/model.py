@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from .config import cfg
 from . import arch, lib, train_ops
-from .engine import Plan
+from .engine import Plan, plan_options
 from .layers import (RepVGGBlock, RepHDW, MPRep, SPPF, ConvWrapper, Concat, Head_DepthUni, Out)
 
 
@@ -366,6 +366,17 @@ class Model(nn.Module):
         ent[1] = _tape.StepTape(ex, x.device)
         return ent[1]
 
+    def plan_key(self, shape, dt, in_dt, device_index, head_feats=False, slot=0):
+        """What plan_for caches a plan under: everything a plan of this model depends on besides the weights (a pure function of the settings: no tensor needed).
+        The options are the record Plan itself resolves and stores (engine.plan_options), so a setting that changes a plan cannot be missing here; `autotune`
+        stands beside it because a tuned plan is another plan even where no option moves (the modes choose_fusion measures for it are not in the key: they
+        follow from the settings that are).  `head_feats` is in the key in its own right as well as through `fuse_head`, so a model whose head cannot take the
+        fused tail (fp32, nc != 80) keeps one plan per value of it: two equal launch lists over arenas of their own."""
+        opts = plan_options(self, dt, None, bool(getattr(self, "fuse_head", True)) and not head_feats, None)
+        if not isinstance(opts.fuse, (str, int)):              # a {name: mode} dict or a collection of names: not hashable as it is
+            opts = opts._replace(fuse=repr(opts.fuse))
+        return (*shape, dt, in_dt, device_index, slot, bool(head_feats), bool(self.autotune), opts)
+
     def plan_for(self, x, head_feats=False, slot=0):
         """head_feats: the caller wants the per-level cls / reg tensors (featmaps): plan without the fused head tail.
         slot: plans of different slots own different activation arenas, so forwards of different slots may be in flight at the same time
@@ -389,8 +400,7 @@ class Model(nn.Module):
             dt = lib.F32
         else:
             dt = lib.F32 if x.dtype == torch.float32 else lib.F16
-        fuse_head = bool(getattr(self, "fuse_head", True)) and not head_feats
-        key = (B, H, W, dt, in_dt, x.device.index, fuse_head, slot, repr(getattr(self, "fuse_stem", True)), repr(self.fuse_bottlenecks), repr(getattr(self, "fuse_tail", "auto")), self.multi_stream, bool(getattr(self, "twin_convs", True)))
+        key = self.plan_key((B, H, W), dt, in_dt, x.device.index, head_feats, slot)
         ver = self.weights_version()
         if ver != self._plans_version:         # the weights changed in place since the cached plans were packed (EMA update, optimizer step ...)
             self._plans = {}
@@ -403,7 +413,7 @@ class Model(nn.Module):
             if self.autotune and dt == lib.F16 and self.fuse_bottlenecks == "auto":
                 from .engine import choose_fusion
                 fuse = choose_fusion(self, B, H, W, dt, in_dt, x.device, x.contiguous())
-            plan = Plan(self, B, H, W, dt, in_dt, x.device, fuse=fuse, fuse_head=fuse_head)
+            plan = Plan(self, B, H, W, dt, in_dt, x.device, fuse=fuse, fuse_head=key[-1].fuse_head)          # the key's PlanOptions: the switch as already resolved
             if self.autotune and dt == lib.F16:
                 plan.autotune(x.contiguous())
             self._plans[key] = plan
