@@ -404,7 +404,9 @@ int maf_bn_stats(const void* x, int32_t x_stride, int32_t M, int32_t C, int32_t 
  *                        num_batches_tracked per branch as in maf_bn_forward; the other half of every scratch is cleared.
  *   maf_bn_sum_backward  dy = gradient of the sum (the same for every branch): one statistics launch ({sum dy, sum dy xhat_j}), one apply launch writing
  *                        every dz_j; dgamma_j / dbeta_j written, or added when accumulate_affine != 0.  bpart = [2][R][1 + nb][roundup(C,256)] fp32, zeroed
- *                        once by the caller, halves alternating call by call (phase) like maf_bn_backward's scratch. */
+ *                        once by the caller, halves alternating call by call (phase) like maf_bn_backward's scratch.
+ * Both directions take the same (nb, C): C <= 4096 (MAF_E_ARG beyond) and (2 + 5 nb) * C * 4 bytes <= 160 KiB, the backward apply pass's LDS — C <= 3412 / 2408 /
+ * 1860 for nb 2 / 3 / 4 (MAF_E_UNSUPPORTED beyond: nothing is launched, no buffer is touched). */
 int maf_bn_sum_forward(const void* const* z, const int32_t* z_stride, int32_t nb, int32_t M, int32_t C, int32_t dtype,
                        const float* const* gamma, const float* const* beta, float eps, float momentum,
                        float* const* running_mean, float* const* running_var, int64_t* const* num_batches_tracked,

@@ -9,6 +9,19 @@
 //             sum g * xhat_j for all branches (1 + NB reads), one apply pass writes every dz_j = gamma_j rstd_j (g - mean(g) - xhat_j mean(g xhat_j))
 //             (1 + NB reads, NB writes)                                                                (2 + 3 NB passes instead of 5 NB)
 // dgamma_j = sum g xhat_j, dbeta_j = sum g (written or added: a gradient-exchange bucket slice).  fp16 / fp32 NHWC views, fp32 arithmetic, 16-byte accesses.
+//
+// Domain, the same for both directions (check()): 2..4 branches, C a multiple of the 16-byte channel group, C <= 4096 (MAF_E_ARG beyond) and the backward apply
+// pass's (2 + 5 nb) C floats of constants within the 160 KiB of LDS — C <= 3412 / 2408 / 1860 for 2 / 3 / 4 branches (MAF_E_UNSUPPORTED beyond, nothing launched;
+// the forward's nb 2 C floats are then within the 64 KiB a kernel gets without asking).  Before, check() took every C <= 4096: a wider forward launch failed, and a
+// wider backward call failed at its apply launch AFTER its statistics launch had added into the scratch half.
+//
+// Tested to (tests/test_gpu_bn_sum_edges.py, straight through the C ABI on poisoned channel slices, against fp64 on the stored values — tests/bn_sum_ref.py):
+// nb 2 / 3 / 4 x fp16 / fp32 x none / ReLU; 1, 2, 4, 8 channel groups (wave shuffles), 3, 5, 6, 7 and 9 (LDS parking, two slices, the last one short), 257 groups
+// (the second trip of the g0 loop), the largest C of every nb and dtype; M = 1, 2, kU plan - 1 / + 0 / + 1, a ragged chunk over two workgroups, 256, 4096, and
+// 131072 x 64 (the 16-pixels-per-lane grids); R = 1, 16, 64; accumulate_affine 0 / 1; three calls of alternating phase on one scratch.  Backward with mean = 0,
+// rstd = 1, gamma in {+-0.5, +-1, +-2}, integer z / dy: dgamma, dbeta bit for bit (pre + sum) for every M, dz bit for bit for M a power of two, the ReLU's g = 0 at
+// u == 0; real-valued inputs: dz, dgamma, dbeta within 4e-4 (fp32) / 2e-2 (fp16 storage) of max |ref|.  Forward: save_mean bit for bit, save_rstd and the running
+// statistics within one fp32 ulp, out within 2e-4 / 1e-2 (bit for bit where it is an integer by construction), the STATS form's sums exactly those of the stored out.
 #include "maf_common.h"
 
 namespace {
@@ -16,6 +29,7 @@ namespace {
 constexpr int MAXB = 4;
 constexpr int kMaxR = 16;
 constexpr int kU = 2;                                                // pixels per lane in flight (x up to 5 tensors)
+constexpr size_t kMaxLds = 160 * 1024;                               // dynamic LDS the backward apply kernel may ask for (the whole LDS of a gfx950 compute unit)
 
 struct BsArgs {
     const void* z[MAXB]; int zs[MAXB];
@@ -351,6 +365,13 @@ int check(int nb, int M, int C, int dtype, int R) {
     const int N = dtype == MAF_F16 ? 8 : 4;
     MAF_REQUIRE(M > 0 && C > 0 && C % N == 0 && C <= 4096, "bn_sum: C must be a multiple of the 16-byte channel group (<= 4096)");
     MAF_REQUIRE(R >= 1 && R <= 64, "bn_sum: replicas 1..64");
+    // ONE rule for both directions: the backward apply pass keeps (2 + 5 nb) C floats of per-channel constants in LDS and may raise its limit to kMaxLds; the
+    // forward's nb 2 C floats stay below the 64 KiB default wherever that holds (nb C <= 7424).  Refused before anything is launched: a backward call whose apply
+    // launch failed had already added into its scratch half.
+    if ((size_t)(2 + 5 * nb) * C * sizeof(float) > kMaxLds) {
+        maf_set_error("bn_sum: (2 + 5 nb) * C floats of per-channel constants exceed 160 KiB of LDS (C <= 3412 / 2408 / 1860 for 2 / 3 / 4 branches)");
+        return MAF_E_UNSUPPORTED;
+    }
     return 0;
 }
 
@@ -439,7 +460,7 @@ extern "C" int maf_bn_sum_backward(const void* dy, int32_t dy_stride, const void
     {                                                                                              \
         static bool attr = false;                                                                  \
         if (!attr && la > 64 * 1024) {                                                             \
-            if (int rc = maf_check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&bn_sum_bwd_apply_kernel<TT, NBV>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), "hipFuncSetAttribute(bn_sum)")) return rc; \
+            if (int rc = maf_check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&bn_sum_bwd_apply_kernel<TT, NBV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds), "hipFuncSetAttribute(bn_sum)")) return rc; \
             attr = true;                                                                           \
         }                                                                                          \
         hipLaunchKernelGGL((bn_sum_bwd_stats_kernel<TT, NBV>), gs, dim3(256), lds_s, s, a);        \

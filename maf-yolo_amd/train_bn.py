@@ -260,6 +260,12 @@ class _BNSum(torch.autograd.Function):
         return (None, None, *dzs, *[dgb[j, 0] for j in range(nb)], *[dgb[j, 1] for j in range(nb)])
 
 
+def bn_sum_takes(nb, c):
+    """the (branch count, width) domain of csrc/bn_sum.hip (its check()): at most 4096 channels, and the backward apply pass's (2 + 5 nb) * c floats of per-channel
+    constants within the 160 KiB of LDS of a compute unit — one rule for both directions; wider sums go down the bn_act chain"""
+    return 2 <= nb <= 4 and 0 < c <= 4096 and (2 + 5 * nb) * c * 4 <= 160 * 1024
+
+
 def bn_sum(zs, bns, pre_stats=None, act=None, out=None, next_bn=None):
     """act(sum_j bns[j](zs[j])): the branches of a train-form DilatedReparamBlock (act None) or of a RepVGGBlock (act "relu", common.py:224).  CUDA + training mode: csrc/bn_sum.hip (one apply pass forward,
     statistics + apply for all branches backward); otherwise — and for anything the kernel does not take — the chain of bn_act calls with `residual`.
@@ -271,6 +277,7 @@ def bn_sum(zs, bns, pre_stats=None, act=None, out=None, next_bn=None):
     x = zs[0]
     mult = 8 if x.dtype == torch.float16 else 4
     ok = (T.bn_sum_merged and 2 <= nb <= 4 and x.is_cuda and not T.framework_ops and not T._deterministic and x.dtype in T._DT and x.dim() == 4 and x.shape[1] % mult == 0
+          and bn_sum_takes(nb, x.shape[1])
           and all(z.shape == x.shape and z.dtype == x.dtype for z in zs)
           and all(bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None and bn.eps == bns[0].eps and bn.momentum == bns[0].momentum
                   and bn.num_batches_tracked.is_cuda and bn.num_batches_tracked.dtype == torch.int64 for bn in bns))
