@@ -1,15 +1,18 @@
-"""File bytes in, frames out, whatever the kind: the router in front of jpeg.py and png.py.
+"""File bytes in, frames out, whatever the kind: the router in front of jpeg.py, png.py and (opt-in) webp.py.
 
 A folder of the reference's loaders (IMG_FORMATS of yolov6/data/datasets.py, LoadData of yolov6/core/inferer.py) mixes JPEG and PNG files;
 decode(files) sniffs each file's signature, hands the JPEG files to jpeg.decode and the PNG files to png.decode (one call each, so each kind
-keeps its one host -> device copy and its one chain of launches) and returns the frames in input order.
+keeps its one host -> device copy and its one chain of launches) and returns the frames in input order.  With webp=True the RIFF / WEBP files
+of the list go to webp.decode in one call of their own (lossless files; webp.py names what it refuses); without the flag nothing changes.
 """
-from . import jpeg, png, staging
+from . import jpeg, png, staging, webp as webp_codec
 from .lib import MafError
 
 
-def kind(data):
-    """'jpeg' or 'png' by the signature of a file's bytes, else None."""
+def kind(data, webp=False):
+    """'jpeg' or 'png' by the signature of a file's bytes, with webp=True also 'webp' (RIFF....WEBP), else None."""
+    if webp and data[:4] == b"RIFF" and data[8:12] == b"WEBP":
+        return "webp"
     if data[:8] == png.SIGNATURE:
         return "png"
     if data[:2] == b"\xff\xd8":
@@ -17,19 +20,19 @@ def kind(data):
     return None
 
 
-def decode(files, device=None, stream=None, check=True, progressive=False, ignore_orientation=False, interlaced=False, apply_orientation=False):
+def decode(files, device=None, stream=None, check=True, progressive=False, ignore_orientation=False, interlaced=False, apply_orientation=False, webp=False):
     """Decode a list of JPEG and PNG files (bytes-like objects or paths, in any mix) on the device -> a list of uint8 [h_i, w_i, 3] BGR CUDA
     tensors in input order, what cv2.imread returns for each file.  `progressive`, `ignore_orientation` and `apply_orientation` go to jpeg.decode, `interlaced` to
-    png.decode (the last two only when set).  With
+    png.decode (the last two only when set).  webp=True also takes lossless WebP files (webp.decode, which is handed `ignore_orientation` too).  With
     check=False -> (frames, status int32 [len(files)] on the device: each file's status word of its own decoder, merged on `stream` behind the
     decoders' launches) without synchronising."""
     files = list(files)
     if not files:
         raise MafError("frames.decode: no files")
-    datas, groups = [], {"jpeg": [], "png": []}
+    datas, groups = [], {"jpeg": [], "png": [], "webp": []}
     for i, f in enumerate(files):
         d = staging.file_bytes(f)
-        k = kind(d)
+        k = kind(d, webp)
         if k is None:
             raise MafError("%s: neither a JPEG nor a PNG signature" % staging.file_name(f, i))
         datas.append(d)
@@ -43,8 +46,10 @@ def decode(files, device=None, stream=None, check=True, progressive=False, ignor
             if k == "jpeg":
                 got = jpeg.decode(sub, device=device, stream=stream, ignore_orientation=ignore_orientation, check=check, progressive=progressive,
                                   **(dict(apply_orientation=True) if apply_orientation else {}))
-            else:
+            elif k == "png":
                 got = png.decode(sub, device=device, stream=stream, check=check, **(dict(interlaced=True) if interlaced else {}))
+            else:
+                got = webp_codec.decode(sub, device=device, stream=stream, check=check, ignore_orientation=ignore_orientation)
         except MafError as e:
             # the decoders number the files of their own call: say which input each one is
             raise type(e)("%s [%s files of this call are inputs %s]" % (e, k, idx)) from None
@@ -57,7 +62,7 @@ def decode(files, device=None, stream=None, check=True, progressive=False, ignor
     if check:
         return frames
     # The status words were written on `stream` (default: the current one) by the decoders' launches, so they are merged THERE, behind those
-    # launches: the words of the two calls back to back, then brought into input order by an index that travels in a pinned buffer
+    # launches: the words of the decoders' calls back to back, then brought into input order by an index that travels in a pinned buffer
     # (non_blocking: the host does not wait for it either).
     import torch
     dev = words[0].device
