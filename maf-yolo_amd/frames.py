@@ -4,15 +4,28 @@ A folder of the reference's loaders (IMG_FORMATS of yolov6/data/datasets.py, Loa
 decode(files) sniffs each file's signature, hands the JPEG files to jpeg.decode and the PNG files to png.decode (one call each, so each kind
 keeps its one host -> device copy and its one chain of launches) and returns the frames in input order.  With webp=True the RIFF / WEBP files
 of the list go to webp.decode in one call of their own (lossless files; webp.py names what it refuses); without the flag nothing changes.
+With webp=True and lossy=True the files among them whose image chunk is `VP8 ` (lossy) go to webp_lossy.decode instead, again in one call.
 """
-from . import jpeg, png, staging, webp as webp_codec
+from . import jpeg, png, staging, webp as webp_codec, webp_lossy
 from .lib import MafError
 
 
-def kind(data, webp=False):
-    """'jpeg' or 'png' by the signature of a file's bytes, with webp=True also 'webp' (RIFF....WEBP), else None."""
+def _lossy(data):
+    """True where the first image chunk of a RIFF / WEBP file is `VP8 ` (a container webp.riff_chunks refuses is left to webp.decode to name)."""
+    try:
+        for cc, _, _, _ in webp_codec.riff_chunks(data):
+            if cc in (b"VP8 ", b"VP8L"):
+                return cc == b"VP8 "
+    except MafError:
+        pass
+    return False
+
+
+def kind(data, webp=False, lossy=False):
+    """'jpeg' or 'png' by the signature of a file's bytes, with webp=True also 'webp' (RIFF....WEBP) and, with lossy=True as well,
+    'webp_lossy' for such a file with a `VP8 ` image chunk, else None."""
     if webp and data[:4] == b"RIFF" and data[8:12] == b"WEBP":
-        return "webp"
+        return "webp_lossy" if lossy and _lossy(data) else "webp"
     if data[:8] == png.SIGNATURE:
         return "png"
     if data[:2] == b"\xff\xd8":
@@ -20,19 +33,21 @@ def kind(data, webp=False):
     return None
 
 
-def decode(files, device=None, stream=None, check=True, progressive=False, ignore_orientation=False, interlaced=False, apply_orientation=False, webp=False):
+def decode(files, device=None, stream=None, check=True, progressive=False, ignore_orientation=False, interlaced=False, apply_orientation=False, webp=False,
+           lossy=False):
     """Decode a list of JPEG and PNG files (bytes-like objects or paths, in any mix) on the device -> a list of uint8 [h_i, w_i, 3] BGR CUDA
     tensors in input order, what cv2.imread returns for each file.  `progressive`, `ignore_orientation` and `apply_orientation` go to jpeg.decode, `interlaced` to
-    png.decode (the last two only when set).  webp=True also takes lossless WebP files (webp.decode, which is handed `ignore_orientation` too).  With
+    png.decode (the last two only when set).  webp=True also takes lossless WebP files (webp.decode, which is handed `ignore_orientation` too),
+    webp=True with lossy=True lossy ones as well (webp_lossy.decode, handed the same).  With
     check=False -> (frames, status int32 [len(files)] on the device: each file's status word of its own decoder, merged on `stream` behind the
     decoders' launches) without synchronising."""
     files = list(files)
     if not files:
         raise MafError("frames.decode: no files")
-    datas, groups = [], {"jpeg": [], "png": [], "webp": []}
+    datas, groups = [], {"jpeg": [], "png": [], "webp": [], "webp_lossy": []}
     for i, f in enumerate(files):
         d = staging.file_bytes(f)
-        k = kind(d, webp)
+        k = kind(d, webp, lossy) if lossy else kind(d, webp)
         if k is None:
             raise MafError("%s: neither a JPEG nor a PNG signature" % staging.file_name(f, i))
         datas.append(d)
@@ -48,8 +63,10 @@ def decode(files, device=None, stream=None, check=True, progressive=False, ignor
                                   **(dict(apply_orientation=True) if apply_orientation else {}))
             elif k == "png":
                 got = png.decode(sub, device=device, stream=stream, check=check, **(dict(interlaced=True) if interlaced else {}))
-            else:
+            elif k == "webp":
                 got = webp_codec.decode(sub, device=device, stream=stream, check=check, ignore_orientation=ignore_orientation)
+            else:
+                got = webp_lossy.decode(sub, device=device, stream=stream, check=check, ignore_orientation=ignore_orientation)
         except MafError as e:
             # the decoders number the files of their own call: say which input each one is
             raise type(e)("%s [%s files of this call are inputs %s]" % (e, k, idx)) from None

@@ -53,9 +53,9 @@ _STATUS_TEXT = ((STATUS_INPUT_EXHAUSTED, "a bit stream that ends early"), (STATU
                 (STATUS_COPY_PAST_END, "a copy that runs past the last pixel"), (STATUS_TABLE_SPACE, "more prefix codes than the stream length allows for"))
 
 
-def parse(data):
-    """Walk the RIFF chunks of one WebP file (bytes-like or a path) and read the VP8L header -> WebpInfo.  Host only."""
-    d = file_bytes(data)
+def riff_chunks(d):
+    """The chunks of a RIFF / WEBP file in file order: (fourcc, first byte of the body, length of the body, offset of the chunk header).
+    MafError where the container is broken, raised when the walk gets there.  webp_lossy.parse walks with it too."""
     n = len(d)
     if n < 12 or d[:4] != b"RIFF" or d[8:12] != b"WEBP":
         raise MafError("webp: no RIFF / WEBP signature at the start (not a WebP file)")
@@ -63,8 +63,6 @@ def parse(data):
     if riff_end > n:
         raise MafError("webp: the RIFF size runs past the end of the file")
     p = 12
-    image = canvas = orientation = None
-    extended = False
     while p < riff_end:
         if p + 8 > riff_end:
             raise MafError("webp: a chunk header runs past the end of the file")
@@ -73,24 +71,44 @@ def parse(data):
         body = p + 8
         if body + L > riff_end:
             raise MafError("webp: chunk %r runs past the end of the file" % cc.decode("latin-1"))
+        yield cc, body, L, p
+        p = body + L + (L & 1)
+
+
+def vp8x_canvas(d, body, L, p):
+    """The canvas (w, h) of a VP8X chunk; a misplaced or malformed one is a MafError, the animation flag WebpUnsupported."""
+    if L < 10 or p != 12:
+        raise MafError("webp: a misplaced or malformed VP8X chunk")
+    if d[body] & 0x02:
+        raise WebpUnsupported("webp: an animation (the VP8X animation flag) is not supported")
+    return int.from_bytes(d[body + 4:body + 7], "little") + 1, int.from_bytes(d[body + 7:body + 10], "little") + 1
+
+
+def exif_orientation(d, body, L, before):
+    """The orientation tag of an EXIF chunk, or `before` where it has none."""
+    seg = d[body:body + L]
+    o = jpeg._exif_orientation(seg if seg[:6] == b"Exif\x00\x00" else b"Exif\x00\x00" + seg)
+    return o if o is not None else before
+
+
+def parse(data):
+    """Walk the RIFF chunks of one WebP file (bytes-like or a path) and read the VP8L header -> WebpInfo.  Host only."""
+    d = file_bytes(data)
+    n = len(d)
+    image = canvas = orientation = None
+    extended = False
+    for cc, body, L, p in riff_chunks(d):
         if cc == b"VP8 " or cc == b"ALPH":
             raise WebpUnsupported("webp: a lossy file (a %r chunk) is not supported (lossless VP8L only)" % cc.decode("latin-1"))
         if cc in (b"ANIM", b"ANMF"):
             raise WebpUnsupported("webp: an animation (an %s chunk) is not supported" % cc.decode("latin-1"))
         if cc == b"VP8X":
-            if L < 10 or p != 12:
-                raise MafError("webp: a misplaced or malformed VP8X chunk")
-            if d[body] & 0x02:
-                raise WebpUnsupported("webp: an animation (the VP8X animation flag) is not supported")
+            canvas = vp8x_canvas(d, body, L, p)
             extended = True
-            canvas = (int.from_bytes(d[body + 4:body + 7], "little") + 1, int.from_bytes(d[body + 7:body + 10], "little") + 1)
         elif cc == b"VP8L" and image is None:
             image = (body, body + L)
         elif cc == b"EXIF":
-            seg = d[body:body + L]
-            o = jpeg._exif_orientation(seg if seg[:6] == b"Exif\x00\x00" else b"Exif\x00\x00" + seg)
-            orientation = o if o is not None else orientation
-        p = body + L + (L & 1)
+            orientation = exif_orientation(d, body, L, orientation)
     if image is None:
         raise MafError("webp: no image chunk (VP8L)")
     s, e = image
