@@ -21,6 +21,7 @@ from . import webp  # noqa: F401
 from .webp import WebpUnsupported  # noqa: F401
 from . import webp_lossy  # noqa: F401
 from . import tiff  # noqa: F401
+from . import bmp  # noqa: F401
 from . import frames  # noqa: F401
 from .checkpoint import load_checkpoint, reference_state_dict  # noqa: F401
 from .loss import ComputeLoss, task_aligned_assign  # noqa: F401

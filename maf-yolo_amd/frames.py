@@ -6,8 +6,11 @@ keeps its one host -> device copy and its one chain of launches) and returns the
 of the list go to webp.decode in one call of their own (lossless files; webp.py names what it refuses); without the flag nothing changes.
 With webp=True and lossy=True the files among them whose image chunk is `VP8 ` (lossy) go to webp_lossy.decode instead, again in one call.
 With tiff=True the files that begin `II*\\0` or `MM\\0*` go to tiff.decode in one call of their own (tiff.py names what it refuses).
+With bmp=True the files that begin `BM` and name one of bmp.HEADER_SIZES at byte 14 go to bmp.decode in one call of their own (bmp.py names
+what it refuses).  That covers the reference's IMG_FORMATS: an mpo file is a JPEG followed by more JPEGs and goes to jpeg.decode, which
+decodes its first frame (what cv2.imread returns); a dng file stays on the host (tiff.py refuses a file with a DNGVersion tag).
 """
-from . import jpeg, png, staging, tiff as tiff_codec, webp as webp_codec, webp_lossy
+from . import bmp as bmp_codec, jpeg, png, staging, tiff as tiff_codec, webp as webp_codec, webp_lossy
 from .lib import MafError
 
 
@@ -22,9 +25,12 @@ def _lossy(data):
     return False
 
 
-def kind(data, webp=False, lossy=False, tiff=False):
+def kind(data, webp=False, lossy=False, tiff=False, bmp=False):
     """'jpeg' or 'png' by the signature of a file's bytes, with webp=True also 'webp' (RIFF....WEBP) and, with lossy=True as well,
-    'webp_lossy' for such a file with a `VP8 ` image chunk, with tiff=True also 'tiff' (II*\\0 or MM\\0*), else None."""
+    'webp_lossy' for such a file with a `VP8 ` image chunk, with tiff=True also 'tiff' (II*\\0 or MM\\0*), with bmp=True also 'bmp' (BM and a DIB
+    header size bmp.py knows at byte 14), else None."""
+    if bmp and data[:2] == b"BM" and len(data) >= 18 and int.from_bytes(data[14:18], "little") in bmp_codec.HEADER_SIZES:
+        return "bmp"
     if tiff and data[:4] in (b"II*\0", b"MM\0*"):
         return "tiff"
     if webp and data[:4] == b"RIFF" and data[8:12] == b"WEBP":
@@ -37,20 +43,21 @@ def kind(data, webp=False, lossy=False, tiff=False):
 
 
 def decode(files, device=None, stream=None, check=True, progressive=False, ignore_orientation=False, interlaced=False, apply_orientation=False, webp=False,
-           lossy=False, tiff=False):
+           lossy=False, tiff=False, bmp=False):
     """Decode a list of JPEG and PNG files (bytes-like objects or paths, in any mix) on the device -> a list of uint8 [h_i, w_i, 3] BGR CUDA
     tensors in input order, what cv2.imread returns for each file.  `progressive`, `ignore_orientation` and `apply_orientation` go to jpeg.decode, `interlaced` to
     png.decode (the last two only when set).  webp=True also takes lossless WebP files (webp.decode, which is handed `ignore_orientation` too),
-    webp=True with lossy=True lossy ones as well (webp_lossy.decode, handed the same), tiff=True TIFF files (tiff.decode, handed the same).  With
+    webp=True with lossy=True lossy ones as well (webp_lossy.decode, handed the same), tiff=True TIFF files (tiff.decode, handed the same),
+    bmp=True BMP files (bmp.decode).  With
     check=False -> (frames, status int32 [len(files)] on the device: each file's status word of its own decoder, merged on `stream` behind the
     decoders' launches) without synchronising."""
     files = list(files)
     if not files:
         raise MafError("frames.decode: no files")
-    datas, groups = [], {"jpeg": [], "png": [], "webp": [], "webp_lossy": [], "tiff": []}
+    datas, groups = [], {"jpeg": [], "png": [], "webp": [], "webp_lossy": [], "tiff": [], "bmp": []}
     for i, f in enumerate(files):
         d = staging.file_bytes(f)
-        k = "tiff" if tiff and kind(d, tiff=True) == "tiff" else kind(d, webp, lossy) if lossy else kind(d, webp)
+        k = "bmp" if bmp and kind(d, bmp=True) == "bmp" else "tiff" if tiff and kind(d, tiff=True) == "tiff" else kind(d, webp, lossy) if lossy else kind(d, webp)
         if k is None:
             raise MafError("%s: neither a JPEG nor a PNG signature" % staging.file_name(f, i))
         datas.append(d)
@@ -70,6 +77,8 @@ def decode(files, device=None, stream=None, check=True, progressive=False, ignor
                 got = webp_codec.decode(sub, device=device, stream=stream, check=check, ignore_orientation=ignore_orientation)
             elif k == "tiff":
                 got = tiff_codec.decode(sub, device=device, stream=stream, check=check, ignore_orientation=ignore_orientation)
+            elif k == "bmp":
+                got = bmp_codec.decode(sub, device=device, stream=stream, check=check)
             else:
                 got = webp_lossy.decode(sub, device=device, stream=stream, check=check, ignore_orientation=ignore_orientation)
         except MafError as e:
