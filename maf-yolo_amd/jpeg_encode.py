@@ -193,29 +193,8 @@ def encode(frames, quality=95, subsampling="4:2:0", rects=None, stream=None, tap
         raise MafError("jpeg_encode.encode: subsampling is \"4:2:0\" or \"4:4:4\", got %r (4:2:2 and grayscale are not written)" % (subsampling,))
     quality, hs = int(quality), SAMPLING[subsampling]
     frames = staging.frame_list(frames, _FRAME_TEXT)
-    fh = np.array([f.shape[0] for f in frames], np.int64)
+    fi, x1, y1, x2, y2 = staging.rect_list(frames, rects, "jpeg_encode.encode", "JPEG")
     fw = np.array([f.shape[1] for f in frames], np.int64)
-    if rects is None:
-        fi = np.arange(len(frames))
-        x1, y1, x2, y2 = np.zeros_like(fw), np.zeros_like(fh), fw, fh
-    else:
-        ra = np.asarray(rects.cpu() if isinstance(rects, torch.Tensor) else rects)
-        if ra.ndim != 2 or ra.shape[1] != 5 or ra.dtype.kind not in "iu":
-            raise MafError("jpeg_encode.encode: rects is an integer array [R, 5] of (frame index, x1, y1, x2, y2)")
-        if ra.shape[0] == 0:
-            raise MafError("jpeg_encode.encode: no rectangles")
-        fi, x1, y1, x2, y2 = (ra[:, c].astype(np.int64) for c in range(5))
-        bad = np.flatnonzero((fi < 0) | (fi >= len(frames)))
-        if bad.size:
-            raise MafError("jpeg_encode.encode: rectangle %d names frame %d of %d" % (bad[0], fi[bad[0]], len(frames)))
-        bad = np.flatnonzero((x1 < 0) | (y1 < 0) | (x2 > fw[fi]) | (y2 > fh[fi]))
-        if bad.size:
-            k = int(bad[0])
-            raise MafError("jpeg_encode.encode: rectangle %d (%d, %d, %d, %d) lies outside its %d x %d frame" % (k, x1[k], y1[k], x2[k], y2[k], fw[fi[k]], fh[fi[k]]))
-        bad = np.flatnonzero((x2 <= x1) | (y2 <= y1))
-        if bad.size:
-            k = int(bad[0])
-            raise MafError("jpeg_encode.encode: rectangle %d (%d, %d, %d, %d) is empty: there is no JPEG file of an empty image" % (k, x1[k], y1[k], x2[k], y2[k]))
     n = len(fi)
     if n > staging.MAX_FILES:
         raise MafError("jpeg_encode.encode takes up to 65535 files per call")

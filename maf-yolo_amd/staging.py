@@ -8,6 +8,7 @@ What a call of theirs does around its kernels, each piece once:
                           non_blocking host -> device copy, and the pinned buffer lives until the block ends;
   * decode_files          the body of jpeg.decode and png.decode (parse every file, stage, launch, frame views, status words);
   * frame_list            the checks of a list of uint8 [h, w, 3] CUDA frames, worded by the caller;
+  * rect_list             the rectangles of those frames an encoder writes one file each for, checked;
   * file_bytes, file_name, status_text, frame_views, raise_on_status, cuda_device, upload, align: the small change.
 A leaf: it imports lib and numpy only, torch where a function needs the device.
 """
@@ -206,3 +207,32 @@ def frame_list(frames, text, what=None):
         if "pitch" in text and h > 1 and f.stride(0) < 3 * w:
             fail("pitch", i=i, strides=tuple(f.stride()))
     return frames
+
+
+def rect_list(frames, rects, what, kind):
+    """The rectangles an encoder (`what`: its name in messages; `kind`: "JPEG" or "PNG") writes one file each for -> int64 arrays (frame index, x1,
+    y1, x2, y2).  rects None: every frame whole; else a host int array (or tensor) [R, 5] of (frame index, x1, y1, x2, y2), each inside its frame
+    and not empty."""
+    import torch
+    fh = np.array([f.shape[0] for f in frames], np.int64)
+    fw = np.array([f.shape[1] for f in frames], np.int64)
+    if rects is None:
+        return np.arange(len(frames)), np.zeros_like(fw), np.zeros_like(fh), fw, fh
+    ra = np.asarray(rects.cpu() if isinstance(rects, torch.Tensor) else rects)
+    if ra.ndim != 2 or ra.shape[1] != 5 or ra.dtype.kind not in "iu":
+        raise MafError("%s: rects is an integer array [R, 5] of (frame index, x1, y1, x2, y2)" % what)
+    if ra.shape[0] == 0:
+        raise MafError("%s: no rectangles" % what)
+    fi, x1, y1, x2, y2 = (ra[:, c].astype(np.int64) for c in range(5))
+    bad = np.flatnonzero((fi < 0) | (fi >= len(frames)))
+    if bad.size:
+        raise MafError("%s: rectangle %d names frame %d of %d" % (what, bad[0], fi[bad[0]], len(frames)))
+    bad = np.flatnonzero((x1 < 0) | (y1 < 0) | (x2 > fw[fi]) | (y2 > fh[fi]))
+    if bad.size:
+        k = int(bad[0])
+        raise MafError("%s: rectangle %d (%d, %d, %d, %d) lies outside its %d x %d frame" % (what, k, x1[k], y1[k], x2[k], y2[k], fw[fi[k]], fh[fi[k]]))
+    bad = np.flatnonzero((x2 <= x1) | (y2 <= y1))
+    if bad.size:
+        k = int(bad[0])
+        raise MafError("%s: rectangle %d (%d, %d, %d, %d) is empty: there is no %s file of an empty image" % (what, k, x1[k], y1[k], x2[k], y2[k], kind))
+    return fi, x1, y1, x2, y2
