@@ -9,9 +9,16 @@ With tiff=True the files that begin `II*\\0` or `MM\\0*` go to tiff.decode in on
 With bmp=True the files that begin `BM` and name one of bmp.HEADER_SIZES at byte 14 go to bmp.decode in one call of their own (bmp.py names
 what it refuses).  That covers the reference's IMG_FORMATS: an mpo file is a JPEG followed by more JPEGs and goes to jpeg.decode, which
 decodes its first frame (what cv2.imread returns); a dng file stays on the host (tiff.py refuses a file with a DNGVersion tag).
+
+The other way: encode(frames, suffixes) is the router in front of jpeg_encode.py, png_encode.py, tiff_encode.py and bmp_encode.py.  The
+reference's cv2.imwrite(save_path, img_src) picks its encoder by the extension save_path keeps from the source file; so does encode, one call
+per format present.
 """
-from . import bmp as bmp_codec, jpeg, png, staging, tiff as tiff_codec, webp as webp_codec, webp_lossy
+from . import bmp as bmp_codec, bmp_encode, jpeg, jpeg_encode, png, png_encode, staging, tiff as tiff_codec, tiff_encode, webp as webp_codec, webp_lossy
 from .lib import MafError
+
+ENCODERS = {"jpeg": jpeg_encode.encode, "png": png_encode.encode, "tiff": tiff_encode.encode, "bmp": bmp_encode.encode}
+SUFFIX_FORMAT = {".jpg": "jpeg", ".jpeg": "jpeg", ".mpo": "jpeg", ".png": "png", ".tif": "tiff", ".tiff": "tiff", ".bmp": "bmp"}
 
 
 def _lossy(data):
@@ -105,3 +112,48 @@ def decode(files, device=None, stream=None, check=True, progressive=False, ignor
         index = torch.tensor(inverse, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
         status = torch.cat(words).index_select(0, index)
     return frames, status
+
+
+def encode(frames, suffixes, rects=None, **per_format):
+    """Encode frames (a list of uint8 [h, w, 3] BGR CUDA tensors, or one [B, h, w, 3] tensor) to files on the device, each in the format its
+    suffix names -> list[bytes] in input order.  `suffixes`: one per output file (per frame, or per rectangle where `rects`, a host int array
+    [R, 5] of (frame index, x1, y1, x2, y2), is given), taken case-insensitively as cv2.imwrite takes save_path's: .jpg / .jpeg / .mpo go to
+    jpeg_encode.encode, .png to png_encode.encode, .tif / .tiff to tiff_encode.encode, .bmp to bmp_encode.encode, in one call per format
+    present.  `per_format`: jpeg=, png=, tiff=, bmp=, each a dict of keyword arguments for that encoder (quality, filter, rows_per_strip,
+    stream, ...).  Reading the files back is where this synchronises, once per format.  Any other suffix (.webp, .dng, ...) raises."""
+    import numpy as np
+    import torch
+    if not torch.is_tensor(frames):                          # a [B, h, w, 3] tensor is indexed like the list; the encoders make every check of the frames
+        frames = list(frames)
+    unknown = sorted(set(per_format) - set(ENCODERS))
+    if unknown:
+        raise MafError("frames.encode: per-format arguments are jpeg=, png=, tiff= and bmp=, got %s" % ", ".join(unknown))
+    suffixes = [suffixes] if isinstance(suffixes, str) else list(suffixes)
+    ra = None
+    if rects is not None:
+        ra = np.asarray(rects.cpu() if isinstance(rects, torch.Tensor) else rects)
+    n = len(frames) if ra is None else len(ra)
+    if len(suffixes) != n:
+        raise MafError("frames.encode: %d suffixes for %d files (one per %s)" % (len(suffixes), n, "frame" if ra is None else "rectangle"))
+    groups = {}
+    for i, sfx in enumerate(suffixes):
+        fmt = SUFFIX_FORMAT.get(sfx.lower()) if isinstance(sfx, str) else None
+        if fmt is None:
+            raise MafError("frames.encode: file %d has suffix %r: no device encoder exists for it (there is one for %s)" % (i, sfx, ", ".join(SUFFIX_FORMAT)))
+        groups.setdefault(fmt, []).append(i)
+    batches = []
+    for fmt, idx in groups.items():                          # every format's launches are queued before any file is read back
+        kw = dict(per_format.get(fmt) or {})
+        try:
+            if ra is None:
+                batches.append((idx, ENCODERS[fmt]([frames[i] for i in idx], **kw)))
+            else:
+                batches.append((idx, ENCODERS[fmt](frames, rects=ra[idx], **kw)))     # all frames: a rectangle names its frame by the caller's index
+        except MafError as e:
+            # the encoders number the files of their own call: say which input each one is
+            raise type(e)("%s [%s files of this call are inputs %s]" % (e, fmt, idx)) from None
+    files = [None] * n
+    for idx, enc in batches:
+        for i, data in zip(idx, enc.files()):
+            files[i] = data
+    return files
