@@ -17,6 +17,7 @@ from .jpeg import JpegUnsupported  # noqa: F401
 from . import jpeg_encode  # noqa: F401
 from . import png_encode  # noqa: F401
 from . import tiff_encode  # noqa: F401
+from . import webp_encode  # noqa: F401
 from . import bmp_encode  # noqa: F401
 from . import png  # noqa: F401
 from .png import PngUnsupported  # noqa: F401

@@ -12,9 +12,11 @@ decodes its first frame (what cv2.imread returns); a dng file stays on the host 
 
 The other way: encode(frames, suffixes) is the router in front of jpeg_encode.py, png_encode.py, tiff_encode.py and bmp_encode.py.  The
 reference's cv2.imwrite(save_path, img_src) picks its encoder by the extension save_path keeps from the source file; so does encode, one call
-per format present.
+per format present.  With webp_lossless=True (or a dict of webp_encode.encode's keyword arguments) the .webp files of the call go to
+webp_encode.encode in one call of their own (lossless VP8L, what cv2.imwrite writes without parameters; webp_encode.py names what it does not
+claim); without it .webp is refused as before.
 """
-from . import bmp as bmp_codec, bmp_encode, jpeg, jpeg_encode, png, png_encode, staging, tiff as tiff_codec, tiff_encode, webp as webp_codec, webp_lossy
+from . import bmp as bmp_codec, bmp_encode, jpeg, jpeg_encode, png, png_encode, staging, tiff as tiff_codec, tiff_encode, webp as webp_codec, webp_encode, webp_lossy
 from .lib import MafError
 
 ENCODERS = {"jpeg": jpeg_encode.encode, "png": png_encode.encode, "tiff": tiff_encode.encode, "bmp": bmp_encode.encode}
@@ -114,13 +116,15 @@ def decode(files, device=None, stream=None, check=True, progressive=False, ignor
     return frames, status
 
 
-def encode(frames, suffixes, rects=None, **per_format):
+def encode(frames, suffixes, rects=None, webp_lossless=None, **per_format):
     """Encode frames (a list of uint8 [h, w, 3] BGR CUDA tensors, or one [B, h, w, 3] tensor) to files on the device, each in the format its
     suffix names -> list[bytes] in input order.  `suffixes`: one per output file (per frame, or per rectangle where `rects`, a host int array
     [R, 5] of (frame index, x1, y1, x2, y2), is given), taken case-insensitively as cv2.imwrite takes save_path's: .jpg / .jpeg / .mpo go to
     jpeg_encode.encode, .png to png_encode.encode, .tif / .tiff to tiff_encode.encode, .bmp to bmp_encode.encode, in one call per format
     present.  `per_format`: jpeg=, png=, tiff=, bmp=, each a dict of keyword arguments for that encoder (quality, filter, rows_per_strip,
-    stream, ...).  Reading the files back is where this synchronises, once per format.  Any other suffix (.webp, .dng, ...) raises."""
+    stream, ...).  `webp_lossless`: None refuses .webp; True, or a dict of keyword arguments for webp_encode.encode (predictor_bits, stream),
+    sends the .webp files to it, in one call, in input order with the rest.  Reading the files back is where this synchronises, once per
+    format.  Any other suffix (.webp without webp_lossless, .dng, ...) raises."""
     import numpy as np
     import torch
     if not torch.is_tensor(frames):                          # a [B, h, w, 3] tensor is indexed like the list; the encoders make every check of the frames
@@ -128,6 +132,12 @@ def encode(frames, suffixes, rects=None, **per_format):
     unknown = sorted(set(per_format) - set(ENCODERS))
     if unknown:
         raise MafError("frames.encode: per-format arguments are jpeg=, png=, tiff= and bmp=, got %s" % ", ".join(unknown))
+    if webp_lossless is not None and webp_lossless is not True and not isinstance(webp_lossless, dict):
+        raise MafError("frames.encode: webp_lossless is None, True or a dict of keyword arguments for webp_encode.encode, got %r" % (webp_lossless,))
+    encoders, suffix_format = ENCODERS, SUFFIX_FORMAT
+    if webp_lossless is not None:
+        encoders, suffix_format = dict(ENCODERS, webp=webp_encode.encode), dict(SUFFIX_FORMAT, **{".webp": "webp"})
+        per_format = dict(per_format, webp=webp_lossless if isinstance(webp_lossless, dict) else {})
     suffixes = [suffixes] if isinstance(suffixes, str) else list(suffixes)
     ra = None
     if rects is not None:
@@ -137,18 +147,18 @@ def encode(frames, suffixes, rects=None, **per_format):
         raise MafError("frames.encode: %d suffixes for %d files (one per %s)" % (len(suffixes), n, "frame" if ra is None else "rectangle"))
     groups = {}
     for i, sfx in enumerate(suffixes):
-        fmt = SUFFIX_FORMAT.get(sfx.lower()) if isinstance(sfx, str) else None
+        fmt = suffix_format.get(sfx.lower()) if isinstance(sfx, str) else None
         if fmt is None:
-            raise MafError("frames.encode: file %d has suffix %r: no device encoder exists for it (there is one for %s)" % (i, sfx, ", ".join(SUFFIX_FORMAT)))
+            raise MafError("frames.encode: file %d has suffix %r: no device encoder exists for it (there is one for %s)" % (i, sfx, ", ".join(suffix_format)))
         groups.setdefault(fmt, []).append(i)
     batches = []
     for fmt, idx in groups.items():                          # every format's launches are queued before any file is read back
         kw = dict(per_format.get(fmt) or {})
         try:
             if ra is None:
-                batches.append((idx, ENCODERS[fmt]([frames[i] for i in idx], **kw)))
+                batches.append((idx, encoders[fmt]([frames[i] for i in idx], **kw)))
             else:
-                batches.append((idx, ENCODERS[fmt](frames, rects=ra[idx], **kw)))     # all frames: a rectangle names its frame by the caller's index
+                batches.append((idx, encoders[fmt](frames, rects=ra[idx], **kw)))     # all frames: a rectangle names its frame by the caller's index
         except MafError as e:
             # the encoders number the files of their own call: say which input each one is
             raise type(e)("%s [%s files of this call are inputs %s]" % (e, fmt, idx)) from None
