@@ -14,9 +14,11 @@ The other way: encode(frames, suffixes) is the router in front of jpeg_encode.py
 reference's cv2.imwrite(save_path, img_src) picks its encoder by the extension save_path keeps from the source file; so does encode, one call
 per format present.  With webp_lossless=True (or a dict of webp_encode.encode's keyword arguments) the .webp files of the call go to
 webp_encode.encode in one call of their own (lossless VP8L, what cv2.imwrite writes without parameters; webp_encode.py names what it does not
-claim); without it .webp is refused as before.
+claim); with webp_lossy=True (or a dict of webp_lossy_encode.encode's keyword arguments: quality, base_q, filter_level, ...) they go to
+webp_lossy_encode.encode instead (lossy VP8, what cv2.imwrite writes with IMWRITE_WEBP_QUALITY); giving both is an error; without either .webp
+is refused as before.
 """
-from . import bmp as bmp_codec, bmp_encode, jpeg, jpeg_encode, png, png_encode, staging, tiff as tiff_codec, tiff_encode, webp as webp_codec, webp_encode, webp_lossy
+from . import bmp as bmp_codec, bmp_encode, jpeg, jpeg_encode, png, png_encode, staging, tiff as tiff_codec, tiff_encode, webp as webp_codec, webp_encode, webp_lossy, webp_lossy_encode
 from .lib import MafError
 
 ENCODERS = {"jpeg": jpeg_encode.encode, "png": png_encode.encode, "tiff": tiff_encode.encode, "bmp": bmp_encode.encode}
@@ -116,14 +118,15 @@ def decode(files, device=None, stream=None, check=True, progressive=False, ignor
     return frames, status
 
 
-def encode(frames, suffixes, rects=None, webp_lossless=None, **per_format):
+def encode(frames, suffixes, rects=None, webp_lossless=None, webp_lossy=None, **per_format):
     """Encode frames (a list of uint8 [h, w, 3] BGR CUDA tensors, or one [B, h, w, 3] tensor) to files on the device, each in the format its
     suffix names -> list[bytes] in input order.  `suffixes`: one per output file (per frame, or per rectangle where `rects`, a host int array
     [R, 5] of (frame index, x1, y1, x2, y2), is given), taken case-insensitively as cv2.imwrite takes save_path's: .jpg / .jpeg / .mpo go to
     jpeg_encode.encode, .png to png_encode.encode, .tif / .tiff to tiff_encode.encode, .bmp to bmp_encode.encode, in one call per format
     present.  `per_format`: jpeg=, png=, tiff=, bmp=, each a dict of keyword arguments for that encoder (quality, filter, rows_per_strip,
     stream, ...).  `webp_lossless`: None refuses .webp; True, or a dict of keyword arguments for webp_encode.encode (predictor_bits, stream),
-    sends the .webp files to it, in one call, in input order with the rest.  Reading the files back is where this synchronises, once per
+    sends the .webp files to it, in one call, in input order with the rest.  `webp_lossy`: likewise for webp_lossy_encode.encode (quality,
+    base_q, filter_level, log2_parts, stream); webp_lossless and webp_lossy together are an error.  Reading the files back is where this synchronises, once per
     format.  Any other suffix (.webp without webp_lossless, .dng, ...) raises."""
     import numpy as np
     import torch
@@ -138,6 +141,13 @@ def encode(frames, suffixes, rects=None, webp_lossless=None, **per_format):
     if webp_lossless is not None:
         encoders, suffix_format = dict(ENCODERS, webp=webp_encode.encode), dict(SUFFIX_FORMAT, **{".webp": "webp"})
         per_format = dict(per_format, webp=webp_lossless if isinstance(webp_lossless, dict) else {})
+    if webp_lossy is not None:
+        if webp_lossy is not True and not isinstance(webp_lossy, dict):
+            raise MafError("frames.encode: webp_lossy is None, True or a dict of keyword arguments for webp_lossy_encode.encode, got %r" % (webp_lossy,))
+        if webp_lossless is not None:
+            raise MafError("frames.encode: webp_lossless and webp_lossy are both given: a .webp file is written one way")
+        encoders, suffix_format = dict(ENCODERS, webp=webp_lossy_encode.encode), dict(SUFFIX_FORMAT, **{".webp": "webp"})
+        per_format = dict(per_format, webp=webp_lossy if isinstance(webp_lossy, dict) else {})
     suffixes = [suffixes] if isinstance(suffixes, str) else list(suffixes)
     ra = None
     if rects is not None:

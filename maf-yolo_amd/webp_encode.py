@@ -17,7 +17,7 @@ What is claimed: the files are legal VP8L and decode, through libwebp (Pillow) a
 rule book's.  cv2.imwrite's own bytes are UNCHECKED and NOT claimed: libwebp's encoder follows heuristics (method, quality, entropy-image search,
 cache sizing) that no specification fixes.  No CPU fallback.
 The output buffer is sized from _worst_case_bytes.
-Not done: lossy WebP (VP8); alpha output; byte parity with libwebp's encoder; the cross-colour transform, colour indexing, the colour cache,
+Lossy WebP (VP8) is written by webp_lossy_encode.py.  Not done: alpha output; byte parity with libwebp's encoder; the cross-colour transform, colour indexing, the colour cache,
 entropy images (more than one code group), backward references other than runs; VP8X, ICC / EXIF / XMP chunks; animation.
 """
 import ctypes as C
